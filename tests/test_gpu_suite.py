@@ -235,6 +235,46 @@ def test_bench_smoke_json():
     assert data["n_gpus"] == 1 and data["value"] > 0
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's buffers as float32 .npy, from
+    seeded inputs (so the expected values are known here without a second
+    bench run), and a plain run carries no diagnostic components."""
+    import json
+
+    import numpy as np
+
+    import bench
+    from hpc_patterns_amd import ops
+    from hpc_patterns_amd.models import SMOKE_CONFIG
+
+    out = tmp_path / "dump"
+    res = _run([sys.executable, str(REPO / "bench.py"), "--steps", "2",
+                "--warmup", "1", "--smoke", "--dump-outputs", str(out)])
+    assert res.returncode == 0, res.stdout + res.stderr
+    data = json.loads([l for l in res.stdout.splitlines()
+                       if l.startswith("{")][-1])
+    assert data["components"] == {}
+    assert data["steps"] == 2 and data["ms_per_step"] > 0
+
+    arrays = {p.stem: np.load(p) for p in out.iterdir()}
+    assert sorted(arrays) == ["compute_out", "d2d_dst", "d2h_host", "h2d_dev"]
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    cfg = SMOKE_CONFIG
+    assert arrays["d2d_dst"].size == cfg["d2d_floats"]
+    assert np.all(arrays["d2d_dst"] == 1.0)
+    assert arrays["d2h_host"].size == cfg["d2h_bytes"] // 4
+    assert np.all(arrays["d2h_host"] == 2.0)
+    expect_h2d = np.random.default_rng(bench._INPUT_SEED).random(
+        cfg["h2d_bytes"] // 4, dtype=np.float32)
+    assert np.array_equal(arrays["h2d_dev"], expect_h2d)
+    ref = torch.empty(cfg["compute_globalsize"], dtype=torch.float32,
+                      device="cuda")
+    ops.busy_wait(ref, cfg["tripcount"], cfg["compute_globalsize"])
+    torch.cuda.synchronize()
+    assert np.array_equal(arrays["compute_out"], ref.cpu().numpy())
+
+
 def test_bin_interop():
     res = _run([str(REPO / "bin/hpk_interop")])
     assert res.returncode == 0, res.stdout + res.stderr
