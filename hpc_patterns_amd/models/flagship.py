@@ -12,6 +12,15 @@ One "step" per GPU, all submitted concurrently on separate hipStreams
                  exchange (ncclSend/Recv over xGMI) — the reference's
                  C4/C5/C1 communication patterns
 
+The four local commands are submitted and joined by one native object
+(StepPlan, native/step.hip): agents, engine ids and completion signals are
+resolved once with the device idle, both engine copies go out back to back
+and ahead of the kernels, and the join spins on the two signals. The
+device-wide sync after the join stays: it measured 5 us on an already-idle
+device (profiles/flagship_link_idle.md). HPK_STEP_PLAN=0 keeps the earlier
+one-call-per-command path (sdma_copy_begin/sdma_wait), which is also what
+calibration and measure_overlap's serial leg use.
+
 The benchmark value is whole-job aggregate bandwidth: payload bytes moved by
 all ranks divided by step time (max over ranks). Compute contributes no
 bytes — it is there to prove copies and collectives overlap compute, which
@@ -21,6 +30,7 @@ main.cpp:12).
 
 from __future__ import annotations
 
+import os
 import time
 from dataclasses import dataclass, field
 
@@ -105,11 +115,35 @@ class FlagshipPatternStep:
         torch.cuda.synchronize()
         if cfg["tripcount"] == -1:
             cfg["tripcount"] = self._calibrate_tripcount()
+        self.plan = self._build_plan()
+
+    def _build_plan(self):
+        """The native submit/join object for the four local commands
+        (native/step.hip), or None to keep the one-call-per-command path:
+        when HPK_STEP_PLAN=0, or when the two host SDMA engines are not
+        both there (the plan itself refuses then, too)."""
+        if self._sdma_engines < 2 or os.environ.get("HPK_STEP_PLAN") == "0":
+            return None
+        cfg = self.config
+        torch.cuda.synchronize()  # engines are resolved with the device idle
+        return self.hpk.StepPlan(
+            self.device.index or 0,
+            (self.h2d_dev, self.h2d_host, cfg["h2d_bytes"]),
+            (self.d2h_host, self.d2h_dev, cfg["d2h_bytes"]),
+            (self.d2d_dst.data_ptr(), self.d2d_src.data_ptr(),
+             cfg["d2d_floats"] * 4),
+            self.compute_out.data_ptr(), cfg["compute_globalsize"],
+            self.streams[0].cuda_stream, self.streams[1].cuda_stream,
+            time_copies=os.environ.get("HPK_STEP_COPY_TIMES") == "1")
 
     def close(self):
-        """Release the raw native buffers (torch tensors free themselves)."""
+        """Release the plan, then the raw native buffers it points into
+        (torch tensors free themselves)."""
         if getattr(self, "hpk", None) is None:
             return
+        if getattr(self, "plan", None) is not None:
+            self.plan.close()
+            self.plan = None
         torch.cuda.synchronize()
         for attr, free in (("h2d_host", self.hpk.host_free),
                            ("h2d_dev", self.hpk.hip_free),
@@ -189,14 +223,20 @@ class FlagshipPatternStep:
     # ---- the step ----
     def step(self) -> None:
         cfg = self.config
-        s0, s1, s2, s3 = self.streams
-        with torch.cuda.stream(s0):
-            self.ops.busy_wait(self.compute_out, cfg["tripcount"],
-                               cfg["compute_globalsize"], stream=s0)
-        with torch.cuda.stream(s1):
-            self.ops.copy_kernel(self.d2d_dst, self.d2d_src, stream=s1)
-        self._h2d(s2)
-        self._d2h(s3)
+        plan = self.plan
+        if plan is not None:
+            # both engine copies back to back, then the two kernels on
+            # streams 0/1 — one native call (native/step.hip)
+            plan.submit(cfg["tripcount"])
+        else:
+            s0, s1, s2, s3 = self.streams
+            with torch.cuda.stream(s0):
+                self.ops.busy_wait(self.compute_out, cfg["tripcount"],
+                                   cfg["compute_globalsize"], stream=s0)
+            with torch.cuda.stream(s1):
+                self.ops.copy_kernel(self.d2d_dst, self.d2d_src, stream=s1)
+            self._h2d(s2)
+            self._d2h(s3)
 
         if self.distributed:
             # collectives ride torch's comm stream, overlapping the local work
@@ -210,7 +250,10 @@ class FlagshipPatternStep:
                     r.wait()
             ar_work.wait()
 
-        self._wait_copies()
+        if plan is not None:
+            plan.join()  # both copies, then streams 0/1
+        else:
+            self._wait_copies()
         # one device-wide sync instead of four per-stream syncs: measurably
         # less host overhead per step, identical semantics at step boundary
         torch.cuda.synchronize()
@@ -252,6 +295,11 @@ class FlagshipPatternStep:
         def concurrent_once():
             s0, s1, s2, s3 = self.streams
             t0 = time.perf_counter()
+            if self.plan is not None:  # the same submission as step()
+                self.plan.submit(cfg["tripcount"])
+                self.plan.join()
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
             with torch.cuda.stream(s0):
                 self.ops.busy_wait(self.compute_out, cfg["tripcount"],
                                    cfg["compute_globalsize"], stream=s0)

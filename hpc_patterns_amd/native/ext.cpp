@@ -258,6 +258,44 @@ PYBIND11_MODULE(_hpk, m) {
     py::gil_scoped_release release;
     hpk::sdma_wait(reinterpret_cast<void*>(handle));
   });
+
+  // ---- step plan: the flagship step's local commands, one submit/join ----
+  py::class_<hpk::StepPlan>(m, "StepPlan")
+      .def(py::init([](int device, std::tuple<uintptr_t, uintptr_t, size_t> h2d,
+                       std::tuple<uintptr_t, uintptr_t, size_t> d2h,
+                       std::tuple<uintptr_t, uintptr_t, size_t> d2d,
+                       uintptr_t busy_out, long busy_globalsize,
+                       uintptr_t busy_stream, uintptr_t copy_stream,
+                       bool time_copies) {
+             auto triple = [](const std::tuple<uintptr_t, uintptr_t, size_t>& t) {
+               return hpk::StepCopy{reinterpret_cast<void*>(std::get<0>(t)),
+                                    reinterpret_cast<const void*>(std::get<1>(t)),
+                                    std::get<2>(t)};
+             };
+             return new hpk::StepPlan(device, triple(h2d), triple(d2h),
+                                      triple(d2d),
+                                      reinterpret_cast<float*>(busy_out),
+                                      busy_globalsize, as_stream(busy_stream),
+                                      as_stream(copy_stream), time_copies);
+           }),
+           py::arg("device"), py::arg("h2d"), py::arg("d2h"), py::arg("d2d"),
+           py::arg("busy_out"), py::arg("busy_globalsize"),
+           py::arg("busy_stream"), py::arg("copy_stream"),
+           py::arg("time_copies") = false,
+           "h2d/d2h/d2d are (dst, src, nbytes) triples of raw pointers")
+      .def("submit", &hpk::StepPlan::submit, py::arg("tripcount"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("join", &hpk::StepPlan::join,
+           py::call_guard<py::gil_scoped_release>())
+      .def("close", &hpk::StepPlan::close,
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("pending", &hpk::StepPlan::pending)
+      .def("copy_times",
+           [](const hpk::StepPlan& p) { return p.copy_times(); },
+           "[(start_ns, end_ns), ...] per engine copy, H2D then D2H per "
+           "submission; empty unless time_copies")
+      .def("clear_copy_times", &hpk::StepPlan::clear_copy_times);
+  m.def("hsa_timestamp_ns", &hpk::hsa_timestamp_ns);
   m.def("trace_push", [](const std::string& n) { hpk::trace_push(n.c_str()); });
   m.def("trace_pop", &hpk::trace_pop);
   m.def("trace_mark", [](const std::string& n) { hpk::trace_mark(n.c_str()); });

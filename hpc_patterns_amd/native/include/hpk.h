@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace hpk {
@@ -215,6 +216,59 @@ int sdma_num_engines_pair(int dst_device, int src_device);
 void* sdma_copy_begin(void* dst, const void* src, size_t nbytes, int device,
                       int engine_index);
 void sdma_wait(void* handle);
+
+// ---------------------------------------------------------------------------
+// Step plan (step.hip) — the flagship step's four local commands behind one
+// submit and one join. Everything that does not change from step to step
+// (owning agents, engine ids, completion signals) is resolved once at
+// construction, so submit() puts both PCIe copies on their engines back to
+// back with no lookup, allocation or status query in between, and only then
+// launches the two kernels: the copy pair is the step's critical path.
+// Not thread-safe: one thread drives a plan.
+// ---------------------------------------------------------------------------
+struct StepCopy {
+  void* dst = nullptr;
+  const void* src = nullptr;
+  size_t nbytes = 0;
+};
+
+class StepPlan {
+ public:
+  // Construct with the device idle (the engine status query reports only
+  // idle engines). Throws if the H2D and D2H copies do not resolve to two
+  // distinct host SDMA engines. time_copies turns on ROCr's async-copy
+  // profiling for the life of the plan (diagnostic; off in normal use).
+  StepPlan(int device, StepCopy h2d, StepCopy d2h, StepCopy d2d,
+           float* busy_out, long busy_globalsize, hipStream_t busy_stream,
+           hipStream_t copy_stream, bool time_copies = false);
+  ~StepPlan();
+  StepPlan(const StepPlan&) = delete;
+  StepPlan& operator=(const StepPlan&) = delete;
+
+  // H2D, D2H (engines), then busy-wait and shader-copy kernels (streams).
+  // Throws if the previous submission was not joined; that submission
+  // stays joinable.
+  void submit(long tripcount);
+  // Waits for both copies, then synchronizes both kernel streams. Returns
+  // at once when nothing is pending.
+  void join();
+  // join() if pending, then destroy the signals. Idempotent.
+  void close();
+  bool pending() const;
+
+  // (start_ns, end_ns) of every engine copy joined so far, H2D then D2H
+  // per submission, on the hsa_timestamp_ns() clock. Empty unless
+  // time_copies was set.
+  const std::vector<std::pair<uint64_t, uint64_t>>& copy_times() const;
+  void clear_copy_times();
+
+ private:
+  struct Impl;
+  Impl* impl_;
+};
+
+// HSA system timestamp in ns — the clock StepPlan::copy_times() is on.
+uint64_t hsa_timestamp_ns();
 
 // ---------------------------------------------------------------------------
 // Tracing (trace.hip) — roctx ranges for rocprofv3 --marker-trace.

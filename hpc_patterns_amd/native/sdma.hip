@@ -13,9 +13,7 @@
 // copies placed on a NAMED DMA engine, independent of runtime heuristics.
 
 #include "include/hpk.h"
-
-#include <hsa/hsa.h>
-#include <hsa/hsa_ext_amd.h>
+#include "include/sdma_route.h"
 
 #include <mutex>
 #include <stdexcept>
@@ -78,6 +76,9 @@ hsa_agent_t agent_for_ptr(const void* ptr, hsa_agent_t gpu_agent,
   return gpu_agent;
 }
 
+} // namespace
+
+namespace detail {
 void check_hsa(hsa_status_t s, const char* what) {
   if (s != HSA_STATUS_SUCCESS) {
     const char* msg = nullptr;
@@ -86,8 +87,8 @@ void check_hsa(hsa_status_t s, const char* what) {
                              (msg ? msg : "?"));
   }
 }
-
-} // namespace
+} // namespace detail
+using detail::check_hsa;
 
 namespace {
 // Engine mask for copies src_agent -> dst_agent. The status API wants the
@@ -132,31 +133,40 @@ int sdma_num_engines(int device) {
   return nh > nd ? nh : nd;
 }
 
+namespace detail {
+SdmaRoute sdma_resolve(const void* dst, const void* src, int device,
+                       int engine_index) {
+  auto& a = agents();
+  if (device < 0 || device >= (int)a.gpus.size())
+    throw std::runtime_error("sdma: bad device");
+  hsa_agent_t gpu = a.gpus[device];
+
+  SdmaRoute r;
+  bool dst_host = false, src_host = false;
+  r.dst_agent = agent_for_ptr(dst, gpu, dst_host);
+  r.src_agent = agent_for_ptr(src, gpu, src_host);
+  if (engine_index >= 0)
+    r.engine = pick_engine_bit(engine_mask_for(r.dst_agent, r.src_agent),
+                               engine_index);
+  return r;
+}
+} // namespace detail
+
 // Begin an explicit-engine async copy; returns an opaque handle to wait on.
 // engine_index < 0 -> let ROCr pick (plain hsa_amd_memory_async_copy).
 void* sdma_copy_begin(void* dst, const void* src, size_t nbytes, int device,
                       int engine_index) {
-  auto& a = agents();
-  if (device < 0 || device >= (int)a.gpus.size())
-    throw std::runtime_error("sdma_copy_begin: bad device");
-  hsa_agent_t gpu = a.gpus[device];
-
-  bool dst_host = false, src_host = false;
-  hsa_agent_t dst_agent = agent_for_ptr(dst, gpu, dst_host);
-  hsa_agent_t src_agent = agent_for_ptr(src, gpu, src_host);
+  detail::SdmaRoute r = detail::sdma_resolve(dst, src, device, engine_index);
+  hsa_agent_t dst_agent = r.dst_agent, src_agent = r.src_agent;
 
   auto* signal = new hsa_signal_t;
   check_hsa(hsa_signal_create(1, 0, nullptr, signal), "hsa_signal_create");
 
   hsa_status_t s = HSA_STATUS_ERROR;
-  if (engine_index >= 0) {
-    uint32_t bit =
-        pick_engine_bit(engine_mask_for(dst_agent, src_agent), engine_index);
-    if (bit != 0) {
-      s = hsa_amd_memory_async_copy_on_engine(
-          dst, dst_agent, src, src_agent, nbytes, 0, nullptr, *signal,
-          (hsa_amd_sdma_engine_id_t)bit, /*force_copy_on_sdma=*/true);
-    }
+  if (r.engine != 0) {
+    s = hsa_amd_memory_async_copy_on_engine(
+        dst, dst_agent, src, src_agent, nbytes, 0, nullptr, *signal,
+        (hsa_amd_sdma_engine_id_t)r.engine, /*force_copy_on_sdma=*/true);
   }
   if (s != HSA_STATUS_SUCCESS) { // no engine requested/available: plain copy
     s = hsa_amd_memory_async_copy(dst, dst_agent, src, src_agent, nbytes, 0,

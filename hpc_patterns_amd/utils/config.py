@@ -46,6 +46,14 @@ KNOBS = [
          "(default 300)", "suite"),
     Knob("HPK_BENCH_FAULT", "fault injection: named bench component raises "
          "(CI rehearsal of null-field degradation)", "suite"),
+    Knob("HPK_STEP_PLAN", "0 = flagship step submits its local commands one "
+         "by one (sdma_copy_begin/sdma_wait) instead of through the native "
+         "StepPlan (default on; A/B switch)", "suite"),
+    Knob("HPK_STEP_WAIT", "StepPlan.join wait policy: spin (default, bounded "
+         "active wait then blocked) | blocked", "suite"),
+    Knob("HPK_STEP_COPY_TIMES", "1 = the flagship step's StepPlan records "
+         "device start/end timestamps of each engine copy (diagnostic)",
+         "suite"),
     Knob("MASTER_ADDR", "torch.distributed rendezvous address (use 127.0.0.1)", "suite"),
     Knob("MASTER_PORT", "torch.distributed rendezvous port", "suite"),
 ]
