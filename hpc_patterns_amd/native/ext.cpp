@@ -112,6 +112,13 @@ PYBIND11_MODULE(_hpk, m) {
         py::arg("c"), py::arg("a"), py::arg("b"), py::arg("a_scale"),
         py::arg("b_scale"), py::arg("m"), py::arg("n"), py::arg("k"),
         py::arg("stream") = 0, py::arg("xcd_swizzle") = 0);
+  m.def("gemm_variant",
+        [](const std::string& kind, long m, long n, long k) {
+          return std::string(hpk::gemm_variant_name(kind.c_str(), m, n, k));
+        },
+        py::arg("kind"), py::arg("m"), py::arg("n"), py::arg("k"),
+        "name of the kernel the gemm_<kind>_nt launcher runs at this shape "
+        "under the current HPK_* environment");
   m.def("copy_kernel",
         [](uintptr_t dst, uintptr_t src, size_t nbytes, uintptr_t stream) {
           hpk::launch_copy_kernel(reinterpret_cast<void*>(dst),
@@ -159,6 +166,26 @@ PYBIND11_MODULE(_hpk, m) {
         [](uintptr_t src, size_t n, uintptr_t stream) {
           py::gil_scoped_release release;
           return hpk::reduce_sum_f32(reinterpret_cast<const float*>(src), n,
+                                     as_stream(stream));
+        },
+        py::arg("src"), py::arg("n"), py::arg("stream") = 0);
+  m.def("fill_i32",
+        [](uintptr_t dst, int value, size_t n, uintptr_t stream) {
+          hpk::launch_fill_i32(reinterpret_cast<int*>(dst), value, n,
+                               as_stream(stream));
+        },
+        py::arg("dst"), py::arg("value"), py::arg("n"), py::arg("stream") = 0);
+  m.def("acc_i32",
+        [](uintptr_t dst, uintptr_t src, size_t n, uintptr_t stream) {
+          hpk::launch_acc_i32(reinterpret_cast<int*>(dst),
+                              reinterpret_cast<const int*>(src), n,
+                              as_stream(stream));
+        },
+        py::arg("dst"), py::arg("src"), py::arg("n"), py::arg("stream") = 0);
+  m.def("reduce_sum_i32",
+        [](uintptr_t src, size_t n, uintptr_t stream) {
+          py::gil_scoped_release release;
+          return hpk::reduce_sum_i32(reinterpret_cast<const int*>(src), n,
                                      as_stream(stream));
         },
         py::arg("src"), py::arg("n"), py::arg("stream") = 0);

@@ -6,7 +6,8 @@
 //   C[M,N] (fp32) = A[M,K] x B[N,K]^T  ("NT": both operands K-contiguous,
 // the natural MFMA feeding order), fp32 accumulate, verified BITWISE
 // against torch fp32 matmul on exactly-representable payloads
-// (tests/test_gpu_kernels.py) and race-screened.
+// (tests/test_gpu_kernels.py; every variant at its edge shapes against a
+// float64 reference in tests/test_gpu_gemm_matrix.py) and race-screened.
 //
 // Members (measured on MI355X, random operands, profiles/gemm_showcase_r2):
 //   k_gemm_bf16_nt<2,2|2,4>   plain two-barrier 128^2 tile; the 8-wave
@@ -1384,46 +1385,150 @@ static int gemm_group(int tiles_n) {
   return 1;
 }
 
+// ---------------------------------------------------------------------------
+// Dispatch: ONE place decides which kernel a (kind, shape, HPK_* env)
+// combination runs. The five launchers switch on gemm_variant_id() and the
+// public gemm_variant_name() (bound as _hpk.gemm_variant) reports the same
+// decision, so a test can assert which kernel it exercised instead of
+// trusting that a default has not moved (tests/test_gpu_gemm_matrix.py).
+// The shape guards live here too: an illegal shape throws from both.
+// ---------------------------------------------------------------------------
+enum class GemmVariant {
+  bf16_plain8, bf16_plain4, bf16_db8, bf16_db4, bf16_8ph,
+  fp8_plain, fp8_8ph, fp8_32,
+  i8_plain, i8_8ph, i8_32,
+  mxfp8_plain, mxfp8_32,
+  mxfp4_w8, mxfp4_w4, mxfp4_db, mxfp4_32, mxfp4_32h,
+};
+
+static const char* const kGemmVariantNames[] = {
+    "bf16_plain8", "bf16_plain4", "bf16_db8", "bf16_db4", "bf16_8ph",
+    "fp8_plain",   "fp8_8ph",     "fp8_32",
+    "i8_plain",    "i8_8ph",      "i8_32",
+    "mxfp8_plain", "mxfp8_32",
+    "mxfp4_w8",    "mxfp4_w4",    "mxfp4_db", "mxfp4_32", "mxfp4_32h",
+};
+
+static GemmVariant gemm_variant_id(const std::string& kind, long M, long N,
+                                   long K) {
+  const bool t256 = M % 256 == 0 && N % 256 == 0;
+  if (kind == "bf16" || kind == "fp8" || kind == "i8") {
+    if (M % BM != 0 || N % BN != 0 || K % BK != 0)
+      throw std::runtime_error("gemm_" + kind +
+                               "_nt requires M,N % 128 == 0 and K % 64 == 0");
+    const char* v = std::getenv("HPK_GEMM_VARIANT");
+    const std::string var = v ? v : "";
+    const bool ph8 = !v || var == "8ph";
+    if (kind == "bf16") {
+      // default: the deep-pipelined 256^2 8-phase kernel wherever its shape
+      // constraints hold (measured 887/1026 TF at 4096^3/8192^3 vs the
+      // plain 8-wave kernel's 777/924; 50 exact-equality race-screen runs
+      // clean). HPK_GEMM_VARIANT=plain|db forces the simpler kernels.
+      if (ph8 && t256 && K % 128 == 0) return GemmVariant::bf16_8ph;
+      // measured (profiles/gemm_r2 logs, random [-1,1) operands): 8 waves
+      // 777/924 TF at 4096^3/8192^3 vs 4 waves 686/765 — the 64x32
+      // sub-tile variant's 76-VGPR budget lifts occupancy 2 -> 6
+      // waves/SIMD and wins everywhere; it is the default.
+      int waves = 8;
+      if (const char* env = std::getenv("HPK_GEMM_WAVES"))
+        waves = std::atoi(env);
+      if (var == "db")
+        return waves == 8 ? GemmVariant::bf16_db8 : GemmVariant::bf16_db4;
+      return waves == 8 ? GemmVariant::bf16_plain8 : GemmVariant::bf16_plain4;
+    }
+    if (kind == "fp8") {
+      // default: the 256^2 32x32x64 scaled-MFMA kernel with hardcoded x1.0
+      // scales (no non-scaled 32x32x64 fp8 MFMA exists) — measured above
+      // the 16x16x128 8-phase pipeline; HPK_GEMM_VARIANT=8ph|plain|db
+      // forces it off
+      if (!v && t256 && K % 128 == 0) return GemmVariant::fp8_32;
+      if (ph8 && t256 && K % 128 == 0) return GemmVariant::fp8_8ph;
+      return GemmVariant::fp8_plain;
+    }
+    // HPK_GEMM_VARIANT=32: the 256^2 32x32x32 kernel — measured NEGATIVE
+    // for i8 (1984/2074 vs the 8-phase 16x16x64 pipeline's 2294/2393 TOPS
+    // at 8192/16384^3: the 16x16x64 instruction already has the same
+    // 16-byte-operand economy and the deep pipeline out-schedules the db
+    // structure); kept selectable, default stays 8ph
+    if (var == "32" && t256 && K % 128 == 0) return GemmVariant::i8_32;
+    if (ph8 && t256 && K % 256 == 0) return GemmVariant::i8_8ph;
+    return GemmVariant::i8_plain;
+  }
+  if (kind == "mxfp8" || kind == "mxfp4") {
+    if (M % 128 != 0 || N % 128 != 0 || K % 128 != 0)
+      throw std::runtime_error("gemm_" + kind +
+                               "_nt requires M,N,K % 128 == 0");
+    if (kind == "mxfp8") {
+      // default: the 256^2 32x32x64 kernel for eligible shapes
+      // (HPK_MX8_VARIANT=plain forces the 128^2 16x16x128 kernel)
+      const char* v8 = std::getenv("HPK_MX8_VARIANT");
+      const bool m32 = !v8 || std::string(v8) == "32";
+      return m32 && t256 ? GemmVariant::mxfp8_32 : GemmVariant::mxfp8_plain;
+    }
+    // variants: 32 (the 256^2-tile 32x32x64 kernel — DEFAULT for
+    // 256-divisible shapes: 2903/3044 TF at 8192^3/16384^3 vs db 2003),
+    // 32h (256x128 tile), db (double-buffered 16x16x128 at 128^2, the
+    // fallback of both), 4 (plain 4-wave — measured negative), anything
+    // else (conventionally 8): the plain 8-wave kernel
+    const char* v = std::getenv("HPK_MX4_WAVES");
+    const std::string waves = v ? v : "32";
+    if (waves == "32" && t256) return GemmVariant::mxfp4_32;
+    if (waves == "32h" && M % 256 == 0) return GemmVariant::mxfp4_32h;
+    if (waves == "db" || waves == "32" || waves == "32h")
+      return GemmVariant::mxfp4_db;
+    if (waves == "4") return GemmVariant::mxfp4_w4;
+    return GemmVariant::mxfp4_w8;
+  }
+  throw std::invalid_argument("unknown gemm kind '" + kind +
+                              "' (bf16|fp8|i8|mxfp8|mxfp4)");
+}
+
+const char* gemm_variant_name(const char* kind, long M, long N, long K) {
+  return kGemmVariantNames[(int)gemm_variant_id(kind ? kind : "", M, N, K)];
+}
+
+// tile order of the 256^2 / 256x128 "32" kernels: row-major unless
+// HPK_GEMM_GROUP is set (measured, 16384^3 interleaved sweep: row-major
+// beats 16/32-wide bands — one resident block/CU makes the concurrent
+// footprint 4 full tile rows, which the MALL already covers)
+static int gemm_group32() {
+  const char* genv = std::getenv("HPK_GEMM_GROUP");
+  return genv ? std::atoi(genv) : 1;
+}
+
 void launch_gemm_i8_nt(int* C, const void* A, const void* B, long M,
                        long N, long K, hipStream_t stream, int xcd_swizzle) {
-  if (M % BM != 0 || N % BN != 0 || K % BK != 0)
-    throw std::runtime_error(
-        "gemm_i8_nt requires M,N % 128 == 0 and K % 64 == 0");
+  const GemmVariant var = gemm_variant_id("i8", M, N, K);
   const int grp = gemm_group((int)(N / 256));
-  const char* var = std::getenv("HPK_GEMM_VARIANT");
-  // HPK_GEMM_VARIANT=32: the 256^2 32x32x32 kernel — measured NEGATIVE
-  // for i8 (1984/2074 vs the 8-phase 16x16x64 pipeline's 2294/2393 TOPS
-  // at 8192/16384^3: the 16x16x64 instruction already has the same
-  // 16-byte-operand economy and the deep pipeline out-schedules the db
-  // structure); kept selectable, default stays 8ph
-  if (var && std::string(var) == "32" && M % 256 == 0 && N % 256 == 0 &&
-      K % 128 == 0) {
+  const signed char* a = (const signed char*)A;
+  const signed char* b = (const signed char*)B;
+  switch (var) {
+  case GemmVariant::i8_32: {
     int tn32 = (int)(N / 256);
     int n32 = (int)(M / 256) * tn32;
-    const char* genv = std::getenv("HPK_GEMM_GROUP");
-    const int grp32 = genv ? std::atoi(genv) : 1;
     hipLaunchKernelGGL(k_gemm_i8_nt_32, dim3(n32), dim3(512), 0, stream, C,
-                       (const signed char*)A, (const signed char*)B, (int)M,
-                       (int)N, (int)K, tn32, n32, xcd_swizzle, grp32);
+                       a, b, (int)M, (int)N, (int)K, tn32, n32, xcd_swizzle,
+                       gemm_group32());
     check_hip(hipGetLastError(), "launch_gemm_i8_nt(32)");
     return;
   }
-  const bool ph8 = !var || std::string(var) == "8ph";
-  if (ph8 && M % 256 == 0 && N % 256 == 0 && K % 256 == 0) {
+  case GemmVariant::i8_8ph: {
     int tn = (int)(N / 256);
     int n8 = (int)(M / 256) * tn;
-    hipLaunchKernelGGL(k_gemm_i8_8ph, dim3(n8), dim3(512), 0, stream, C,
-                       (const signed char*)A, (const signed char*)B, (int)M,
-                       (int)N, (int)K, tn, n8, xcd_swizzle, grp);
+    hipLaunchKernelGGL(k_gemm_i8_8ph, dim3(n8), dim3(512), 0, stream, C, a,
+                       b, (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
     check_hip(hipGetLastError(), "launch_gemm_i8_nt(8ph)");
     return;
   }
-  int tiles_n = (int)(N / BN);
-  int nwg = (int)(M / BM) * tiles_n;
-  hipLaunchKernelGGL((k_gemm_i8_nt<2, 4>), dim3(nwg), dim3(512), 0, stream,
-                     C, (const signed char*)A, (const signed char*)B, (int)M,
-                     (int)N, (int)K, tiles_n, nwg, xcd_swizzle, grp);
-  check_hip(hipGetLastError(), "launch_gemm_i8_nt");
+  default: {
+    int tiles_n = (int)(N / BN);
+    int nwg = (int)(M / BM) * tiles_n;
+    hipLaunchKernelGGL((k_gemm_i8_nt<2, 4>), dim3(nwg), dim3(512), 0, stream,
+                       C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
+    check_hip(hipGetLastError(), "launch_gemm_i8_nt");
+  }
+  }
 }
 
 
@@ -1687,33 +1792,26 @@ __global__ __launch_bounds__(512) void k_gemm_mxfp8_nt_32(
 void launch_gemm_mxfp8_nt(float* C, const void* A, const void* B,
                           const void* As, const void* Bs, long M, long N,
                           long K, hipStream_t stream, int xcd_swizzle) {
-  if (M % 128 != 0 || N % 128 != 0 || K % 128 != 0)
-    throw std::runtime_error("gemm_mxfp8_nt requires M,N,K % 128 == 0");
-  // default: the 256^2 32x32x64 kernel for eligible shapes
-  // (HPK_MX8_VARIANT=plain forces the 128^2 16x16x128 kernel)
-  const char* v8 = std::getenv("HPK_MX8_VARIANT");
-  const bool m32 = (!v8 || std::string(v8) == "32");
-  if (m32 && M % 256 == 0 && N % 256 == 0) {
+  const GemmVariant var = gemm_variant_id("mxfp8", M, N, K);
+  const unsigned char* a = (const unsigned char*)A;
+  const unsigned char* b = (const unsigned char*)B;
+  const unsigned char* as = (const unsigned char*)As;
+  const unsigned char* bs = (const unsigned char*)Bs;
+  if (var == GemmVariant::mxfp8_32) {
     int tn32 = (int)(N / 256);
     int n32 = (int)(M / 256) * tn32;
-    const char* genv = std::getenv("HPK_GEMM_GROUP");
-    const int grp32 = genv ? std::atoi(genv) : 1; // row-major (as mx4 _32)
     hipLaunchKernelGGL((k_gemm_mxfp8_nt_32<true>), dim3(n32), dim3(512), 0,
-                       stream,
-                       C, (const unsigned char*)A, (const unsigned char*)B,
-                       (const unsigned char*)As, (const unsigned char*)Bs,
-                       (int)M, (int)N, (int)K, tn32, n32, xcd_swizzle,
-                       grp32);
+                       stream, C, a, b, as, bs, (int)M, (int)N, (int)K, tn32,
+                       n32, xcd_swizzle, gemm_group32());
     check_hip(hipGetLastError(), "launch_gemm_mxfp8_nt(32)");
     return;
   }
   const int grp = gemm_group((int)(N / 128));
   int tiles_n = (int)(N / 128);
   int nwg = (int)(M / 128) * tiles_n;
-  hipLaunchKernelGGL(k_gemm_mxfp8_nt, dim3(nwg), dim3(512), 0, stream, C,
-                     (const unsigned char*)A, (const unsigned char*)B,
-                     (const unsigned char*)As, (const unsigned char*)Bs,
-                     (int)M, (int)N, (int)K, tiles_n, nwg, xcd_swizzle, grp);
+  hipLaunchKernelGGL(k_gemm_mxfp8_nt, dim3(nwg), dim3(512), 0, stream, C, a,
+                     b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
+                     xcd_swizzle, grp);
   check_hip(hipGetLastError(), "launch_gemm_mxfp8_nt");
 }
 
@@ -2260,57 +2358,45 @@ __global__ __launch_bounds__(512) void k_gemm_mxfp4_nt_32h(
 void launch_gemm_mxfp4_nt(float* C, const void* A, const void* B,
                           const void* As, const void* Bs, long M, long N,
                           long K, hipStream_t stream, int xcd_swizzle) {
-  if (M % 128 != 0 || N % 128 != 0 || K % 128 != 0)
-    throw std::runtime_error("gemm_mxfp4_nt requires M,N,K % 128 == 0");
+  const GemmVariant var = gemm_variant_id("mxfp4", M, N, K);
+  const unsigned char* a = (const unsigned char*)A;
+  const unsigned char* b = (const unsigned char*)B;
+  const unsigned char* as = (const unsigned char*)As;
+  const unsigned char* bs = (const unsigned char*)Bs;
   const int grp = gemm_group((int)(N / 128));
   int tiles_n = (int)(N / 128);
   int nwg = (int)(M / 128) * tiles_n;
-  // variants: 32 (the 256^2-tile 32x32x64 kernel — DEFAULT for
-  // 256-divisible shapes: 2903/3044 TF at 8192^3/16384^3 vs db 2003),
-  // db (double-buffered 16x16x128 at 128^2, the fallback), 8 (plain
-  // 8-wave), 4 (plain 4-wave — measured negative)
-  const char* v = std::getenv("HPK_MX4_WAVES");
-  std::string waves = v ? v : "32";
-  if (waves == "32" && M % 256 == 0 && N % 256 == 0) {
+  switch (var) {
+  case GemmVariant::mxfp4_32: {
     int tn32 = (int)(N / 256);
     int n32 = (int)(M / 256) * tn32;
-    // measured (16384^3 interleaved sweep): row-major beats 16/32-wide
-    // bands here — one resident block/CU makes the concurrent footprint
-    // 4 full tile rows, which the MALL already covers
-    const char* genv = std::getenv("HPK_GEMM_GROUP");
-    const int grp32 = genv ? std::atoi(genv) : 1;
     hipLaunchKernelGGL(k_gemm_mxfp4_nt_32, dim3(n32), dim3(512), 0, stream,
-                       C, (const unsigned char*)A, (const unsigned char*)B,
-                       (const unsigned char*)As, (const unsigned char*)Bs,
-                       (int)M, (int)N, (int)K, tn32, n32, xcd_swizzle,
-                       grp32);
-  } else if (waves == "32h" && M % 256 == 0) {
+                       C, a, b, as, bs, (int)M, (int)N, (int)K, tn32, n32,
+                       xcd_swizzle, gemm_group32());
+    break;
+  }
+  case GemmVariant::mxfp4_32h: {
     int tnh = (int)(N / 128);
     int nh = (int)(M / 256) * tnh;
-    const char* genv = std::getenv("HPK_GEMM_GROUP");
-    const int grph = genv ? std::atoi(genv) : 1;
     hipLaunchKernelGGL(k_gemm_mxfp4_nt_32h, dim3(nh), dim3(512), 0, stream,
-                       C, (const unsigned char*)A, (const unsigned char*)B,
-                       (const unsigned char*)As, (const unsigned char*)Bs,
-                       (int)M, (int)N, (int)K, tnh, nh, xcd_swizzle, grph);
-  } else if (waves == "db" || waves == "32" || waves == "32h") {
+                       C, a, b, as, bs, (int)M, (int)N, (int)K, tnh, nh,
+                       xcd_swizzle, gemm_group32());
+    break;
+  }
+  case GemmVariant::mxfp4_db:
     hipLaunchKernelGGL(k_gemm_mxfp4_nt_db, dim3(nwg), dim3(512), 0, stream,
-                       C, (const unsigned char*)A, (const unsigned char*)B,
-                       (const unsigned char*)As, (const unsigned char*)Bs,
-                       (int)M, (int)N, (int)K, tiles_n, nwg, xcd_swizzle,
-                       grp);
-  } else if (waves == "4") {
+                       C, a, b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
+    break;
+  case GemmVariant::mxfp4_w4:
     hipLaunchKernelGGL(k_gemm_mxfp4_nt_w4, dim3(nwg), dim3(256), 0, stream,
-                       C, (const unsigned char*)A, (const unsigned char*)B,
-                       (const unsigned char*)As, (const unsigned char*)Bs,
-                       (int)M, (int)N, (int)K, tiles_n, nwg, xcd_swizzle,
-                       grp);
-  } else {
+                       C, a, b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
+    break;
+  default:
     hipLaunchKernelGGL(k_gemm_mxfp4_nt, dim3(nwg), dim3(512), 0, stream, C,
-                       (const unsigned char*)A, (const unsigned char*)B,
-                       (const unsigned char*)As, (const unsigned char*)Bs,
-                       (int)M, (int)N, (int)K, tiles_n, nwg, xcd_swizzle,
-                       grp);
+                       a, b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
   }
   check_hip(hipGetLastError(), "launch_gemm_mxfp4_nt");
 }
@@ -2318,95 +2404,76 @@ void launch_gemm_mxfp4_nt(float* C, const void* A, const void* B,
 void launch_gemm_fp8_nt(float* C, const void* A, const void* B, long M,
                         long N, long K, hipStream_t stream,
                         int xcd_swizzle) {
-  if (M % BM != 0 || N % BN != 0 || K % BK != 0)
-    throw std::runtime_error(
-        "gemm_fp8_nt requires M,N % 128 == 0 and K % 64 == 0");
+  const GemmVariant var = gemm_variant_id("fp8", M, N, K);
+  const unsigned char* a = (const unsigned char*)A;
+  const unsigned char* b = (const unsigned char*)B;
   const int grp = gemm_group((int)(N / 256));
-  const char* var = std::getenv("HPK_GEMM_VARIANT");
-  const bool ph8 = !var || std::string(var) == "8ph";
-  // default: the 256^2 32x32x64 scaled-MFMA kernel with hardcoded x1.0
-  // scales (no non-scaled 32x32x64 fp8 MFMA exists) — measured above the
-  // 16x16x128 8-phase pipeline; HPK_GEMM_VARIANT=8ph|plain|db forces it off
-  if (!var && M % 256 == 0 && N % 256 == 0 && K % 128 == 0) {
+  switch (var) {
+  case GemmVariant::fp8_32: {
     int tn32 = (int)(N / 256);
     int n32 = (int)(M / 256) * tn32;
-    const char* genv = std::getenv("HPK_GEMM_GROUP");
-    const int grp32 = genv ? std::atoi(genv) : 1;
     hipLaunchKernelGGL((k_gemm_mxfp8_nt_32<false>), dim3(n32), dim3(512), 0,
-                       stream, C, (const unsigned char*)A,
-                       (const unsigned char*)B, nullptr, nullptr, (int)M,
-                       (int)N, (int)K, tn32, n32, xcd_swizzle, grp32);
+                       stream, C, a, b, nullptr, nullptr, (int)M, (int)N,
+                       (int)K, tn32, n32, xcd_swizzle, gemm_group32());
     check_hip(hipGetLastError(), "launch_gemm_fp8_nt(32)");
     return;
   }
-  if (ph8 && M % 256 == 0 && N % 256 == 0 && K % 128 == 0) {
+  case GemmVariant::fp8_8ph: {
     int tn = (int)(N / 256);
     int n8 = (int)(M / 256) * tn;
-    hipLaunchKernelGGL(k_gemm_fp8_8ph, dim3(n8), dim3(512), 0, stream, C,
-                       (const unsigned char*)A, (const unsigned char*)B,
-                       (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
+    hipLaunchKernelGGL(k_gemm_fp8_8ph, dim3(n8), dim3(512), 0, stream, C, a,
+                       b, (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
     check_hip(hipGetLastError(), "launch_gemm_fp8_nt(8ph)");
     return;
   }
-  int tiles_m = (int)(M / BM), tiles_n = (int)(N / BN);
-  int nwg = tiles_m * tiles_n;
-  hipLaunchKernelGGL((k_gemm_fp8_nt<2, 4>), dim3(nwg), dim3(512), 0, stream,
-                     C, (const unsigned char*)A, (const unsigned char*)B,
-                     (int)M, (int)N, (int)K, tiles_n, nwg, xcd_swizzle, grp);
-  check_hip(hipGetLastError(), "launch_gemm_fp8_nt");
+  default: {
+    int tiles_n = (int)(N / BN);
+    int nwg = (int)(M / BM) * tiles_n;
+    hipLaunchKernelGGL((k_gemm_fp8_nt<2, 4>), dim3(nwg), dim3(512), 0, stream,
+                       C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
+    check_hip(hipGetLastError(), "launch_gemm_fp8_nt");
+  }
+  }
 }
 
 void launch_gemm_bf16_nt(float* C, const void* A, const void* B, long M,
                          long N, long K, hipStream_t stream,
                          int xcd_swizzle) {
-  if (M % BM != 0 || N % BN != 0 || K % BK != 0)
-    throw std::runtime_error(
-        "gemm_bf16_nt requires M,N % 128 == 0 and K % 64 == 0");
+  const GemmVariant var = gemm_variant_id("bf16", M, N, K);
+  const __hip_bfloat16* a = (const __hip_bfloat16*)A;
+  const __hip_bfloat16* b = (const __hip_bfloat16*)B;
   const int grp = gemm_group((int)(N / 256));
-  int tiles_m = (int)(M / BM), tiles_n = (int)(N / BN);
-  int nwg = tiles_m * tiles_n;
-  // measured (profiles/gemm_r2 logs, random [-1,1) operands): 8 waves
-  // 777/924 TF at 4096^3/8192^3 vs 4 waves 686/765 — the 64x32 sub-tile
-  // variant's 76-VGPR budget lifts occupancy 2 -> 6 waves/SIMD and wins
-  // everywhere; it is the default.
-  int waves = 8;
-  if (const char* env = std::getenv("HPK_GEMM_WAVES")) waves = std::atoi(env);
-  const char* var = std::getenv("HPK_GEMM_VARIANT");
-  const bool dbuf = var && std::string(var) == "db";
-  // default: the deep-pipelined 256^2 8-phase kernel wherever its shape
-  // constraints hold (measured 887/1026 TF at 4096^3/8192^3 vs the plain
-  // 8-wave kernel's 777/924; 50 exact-equality race-screen runs clean).
-  // HPK_GEMM_VARIANT=plain|db forces the simpler kernels.
-  const bool ph8 = !var || std::string(var) == "8ph";
-  if (ph8 && M % 256 == 0 && N % 256 == 0 && K % 128 == 0) {
+  int tiles_n = (int)(N / BN);
+  int nwg = (int)(M / BM) * tiles_n;
+  switch (var) {
+  case GemmVariant::bf16_8ph: {
     int tn = (int)(N / 256);
     int n8 = (int)(M / 256) * tn;
-    hipLaunchKernelGGL(k_gemm_bf16_8ph, dim3(n8), dim3(512), 0, stream, C,
-                       (const __hip_bfloat16*)A, (const __hip_bfloat16*)B,
-                       (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
+    hipLaunchKernelGGL(k_gemm_bf16_8ph, dim3(n8), dim3(512), 0, stream, C, a,
+                       b, (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
     check_hip(hipGetLastError(), "launch_gemm_bf16_nt(8ph)");
     return;
   }
-  if (dbuf && waves == 8) {
+  case GemmVariant::bf16_db8:
     hipLaunchKernelGGL((k_gemm_bf16_nt_db<2, 4>), dim3(nwg), dim3(512), 0,
-                       stream, C, (const __hip_bfloat16*)A,
-                       (const __hip_bfloat16*)B, (int)M, (int)N, (int)K,
-                       tiles_n, nwg, xcd_swizzle, grp);
-  } else if (dbuf) {
+                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
+    break;
+  case GemmVariant::bf16_db4:
     hipLaunchKernelGGL((k_gemm_bf16_nt_db<2, 2>), dim3(nwg), dim3(256), 0,
-                       stream, C, (const __hip_bfloat16*)A,
-                       (const __hip_bfloat16*)B, (int)M, (int)N, (int)K,
-                       tiles_n, nwg, xcd_swizzle, grp);
-  } else if (waves == 8) {
+                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
+    break;
+  case GemmVariant::bf16_plain8:
     hipLaunchKernelGGL((k_gemm_bf16_nt<2, 4>), dim3(nwg), dim3(512), 0,
-                       stream, C, (const __hip_bfloat16*)A,
-                       (const __hip_bfloat16*)B, (int)M, (int)N, (int)K,
-                       tiles_n, nwg, xcd_swizzle, grp);
-  } else {
+                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
+    break;
+  default:
     hipLaunchKernelGGL((k_gemm_bf16_nt<2, 2>), dim3(nwg), dim3(256), 0,
-                       stream, C, (const __hip_bfloat16*)A,
-                       (const __hip_bfloat16*)B, (int)M, (int)N, (int)K,
-                       tiles_n, nwg, xcd_swizzle, grp);
+                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
+                       xcd_swizzle, grp);
   }
   check_hip(hipGetLastError(), "launch_gemm_bf16_nt");
 }

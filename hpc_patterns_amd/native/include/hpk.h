@@ -100,6 +100,12 @@ void launch_gemm_mxfp8_nt(float* C, const void* A, const void* B,
 void launch_gemm_mxfp4_nt(float* C, const void* A, const void* B,
                           const void* As, const void* Bs, long M, long N,
                           long K, hipStream_t stream, int xcd_swizzle = 0);
+// Host-only: the name of the kernel the launcher for `kind`
+// (bf16|fp8|i8|mxfp8|mxfp4) runs at this shape under the current HPK_*
+// environment — bf16_plain8|plain4|db8|db4|8ph, fp8_plain|8ph|32,
+// i8_plain|8ph|32, mxfp8_plain|32, mxfp4_w8|w4|db|32|32h. The launchers
+// switch on the same decision; illegal shapes and unknown kinds throw.
+const char* gemm_variant_name(const char* kind, long M, long N, long K);
 
 // Exact double-precision sum of n floats. Synchronizes `stream`.
 // Replaces the reference's O(N log N) host sort+sum checksum

@@ -58,12 +58,290 @@ def test_copy_kernel(ops, dev, nbytes):
     assert torch.equal(dst, src)
 
 
-def test_copy_kernel_unaligned_tail(ops, dev):
+def test_copy_kernel_aligned_pointer_odd_length(ops, dev):
     base = torch.rand(1029, device=dev)  # odd length -> 16B body + tail
     dst = torch.empty_like(base)
     ops.copy_kernel(dst, base)
     torch.cuda.synchronize()
     assert torch.equal(dst, base)
+
+
+# ---------------------------------------------------------------------------
+# Streaming kernels at their edges: misaligned pointers (the scalar
+# fallbacks of every launcher), vector-body tails, the unrolled copy body,
+# and a second grid-stride iteration at the benchmark's size regime. Every
+# write target sits inside one larger allocation between 64-byte canaries.
+# ---------------------------------------------------------------------------
+
+_CANARY = 64      # bytes on each side of a write target
+_CANARY_BYTE = 0xA5
+_MISALIGNED_NS = [1, 3, 4, 5, 17, 255, 1025, (1 << 20) + 3]
+_TAIL_NS = [4 * q + r for q in (1, 64, 257) for r in (1, 2, 3)]
+
+
+def _window(dev, nbytes, misalign, dtype):
+    """(base, win): `win` views `nbytes` of the uint8 allocation `base`
+    starting `misalign` bytes past a 16-byte boundary, with >= 64 canary
+    bytes before and after it."""
+    base = torch.full((_CANARY + misalign + nbytes + _CANARY,), _CANARY_BYTE,
+                      dtype=torch.uint8, device=dev)
+    start = _CANARY + misalign
+    win = base[start:start + nbytes].view(dtype)
+    assert win.data_ptr() % 16 == misalign and win.is_contiguous()
+    return base, win
+
+
+def _canaries_intact(base, win):
+    start = win.data_ptr() - base.data_ptr()
+    end = start + win.numel() * win.element_size()
+    assert start >= _CANARY and base.numel() - end >= _CANARY
+    return bool((base[:start] == _CANARY_BYTE).all()) and \
+        bool((base[end:] == _CANARY_BYTE).all())
+
+
+@pytest.mark.parametrize("n,misalign",
+                         [(n, 4) for n in _MISALIGNED_NS] +
+                         [(n, 0) for n in _TAIL_NS])
+def test_fill_misaligned_and_tails(ops, dev, n, misalign):
+    base, t = _window(dev, 4 * n, misalign, torch.float32)
+    ops.fill(t, 3.5)
+    torch.cuda.synchronize()
+    assert torch.equal(t, torch.full((n,), 3.5, device=dev))
+    assert _canaries_intact(base, t)
+
+
+@pytest.mark.parametrize("which", ["dst", "src", "both"])
+@pytest.mark.parametrize("n", _MISALIGNED_NS)
+def test_accumulate_misaligned(ops, dev, n, which):
+    a0 = torch.rand(n, device=dev)
+    b0 = torch.rand(n, device=dev)
+    base, a = _window(dev, 4 * n, 4 if which in ("dst", "both") else 0,
+                      torch.float32)
+    _, b = _window(dev, 4 * n, 4 if which in ("src", "both") else 0,
+                   torch.float32)
+    a.copy_(a0)
+    b.copy_(b0)
+    ops.accumulate(a, b)
+    torch.cuda.synchronize()
+    assert torch.equal(a, a0 + b0)
+    assert torch.equal(b, b0)
+    assert _canaries_intact(base, a)
+
+
+@pytest.mark.parametrize("n", _TAIL_NS)
+def test_accumulate_aligned_tails(ops, dev, n):
+    a0 = torch.rand(n, device=dev)
+    b0 = torch.rand(n, device=dev)
+    base, a = _window(dev, 4 * n, 0, torch.float32)
+    a.copy_(a0)
+    ops.accumulate(a, b0)
+    torch.cuda.synchronize()
+    assert torch.equal(a, a0 + b0)
+    assert _canaries_intact(base, a)
+
+
+@pytest.mark.parametrize("n", _MISALIGNED_NS)
+def test_copy_kernel_misaligned_f32(ops, dev, n):
+    src0 = torch.rand(n, device=dev)
+    _, src = _window(dev, 4 * n, 4, torch.float32)
+    base, dst = _window(dev, 4 * n, 4, torch.float32)
+    src.copy_(src0)
+    ops.copy_kernel(dst, src)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src0)
+    assert _canaries_intact(base, dst)
+
+
+@pytest.mark.parametrize("which", ["dst", "src", "both"])
+@pytest.mark.parametrize("nbytes", [1, 15, 16, 17, 4099])
+def test_copy_kernel_byte_misaligned(ops, dev, nbytes, which):
+    g = torch.Generator(device="cpu").manual_seed(nbytes)
+    src0 = torch.randint(0, 256, (nbytes,), generator=g,
+                         dtype=torch.uint8).to(dev)
+    _, src = _window(dev, nbytes, 1 if which in ("src", "both") else 0,
+                     torch.uint8)
+    base, dst = _window(dev, nbytes, 1 if which in ("dst", "both") else 0,
+                        torch.uint8)
+    src.copy_(src0)
+    ops.copy_kernel(dst, src)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src0)
+    assert _canaries_intact(base, dst)
+
+
+@pytest.mark.parametrize("misalign", [0, 4])
+@pytest.mark.parametrize("n", [2, 3, 5, 6, 7, 1026, 1027, (1 << 20) + 2,
+                               (1 << 20) + 3])
+def test_reduce_sum_tails_and_misaligned(ops, dev, n, misalign):
+    """Integer-valued addends: every partial sum is an exact double, so the
+    device reduction must EQUAL the float64 sum in any order. n % 4 in
+    {2, 3} with n4 > 0 reaches the float4 body's tail lanes; the misaligned
+    base reaches the scalar branch."""
+    import numpy as np
+
+    g = torch.Generator(device="cpu").manual_seed(n)
+    host = torch.randint(-1000, 1001, (n,), generator=g).float()
+    _, t = _window(dev, 4 * n, misalign, torch.float32)
+    t.copy_(host)
+    got = ops.reduce_sum(t)
+    assert got == float(host.numpy().astype(np.float64).sum())
+
+
+def test_reduce_sum_uniform_random_bound(ops, dev):
+    """Non-integer addends: every float32 is an exact double and the
+    reduction only ever adds doubles, so for ANY summation tree
+    |got - exact| <= (n - 1) * u * sum|x| with u = 2^-53."""
+    import math
+
+    n = (1 << 20) + 3
+    g = torch.Generator(device="cpu").manual_seed(20)
+    host = torch.rand(n, generator=g)
+    got = ops.reduce_sum(host.to(dev))
+    xs = host.double().tolist()
+    ref = math.fsum(xs)
+    bound = n * 2.0 ** -53 * math.fsum(abs(x) for x in xs)
+    print(f"reduce_sum err {abs(got - ref):.3e} bound {bound:.3e}")
+    assert abs(got - ref) <= bound
+
+
+@pytest.mark.parametrize("src_offset", [0, 4])
+@pytest.mark.parametrize("cap", [1, 16])
+@pytest.mark.parametrize("unroll", [1, 4, 5])
+def test_copy_kernel_tuned_unrolled_body(ops, dev, unroll, cap, src_offset):
+    """n16 = 9 * stride + 37 with stride = cap * 256 threads: the 4x body
+    of the unrolled kernel runs twice (8 strides), then the remainder loop
+    takes the ninth stride and the 37 leftovers; 5 tail bytes follow. A
+    source 4 bytes off a 16-byte boundary takes the tuned launcher's
+    fallback to the generic copy."""
+    from hpc_patterns_amd._native import native
+
+    hpk = native()
+    n16 = 9 * (cap * 256) + 37
+    nbytes = 16 * n16 + 5
+    g = torch.Generator(device="cpu").manual_seed(unroll * 100 + cap)
+    src0 = torch.randint(0, 256, (nbytes,), generator=g,
+                         dtype=torch.uint8).to(dev)
+    _, src = _window(dev, nbytes, src_offset, torch.uint8)
+    base, dst = _window(dev, nbytes, 0, torch.uint8)
+    src.copy_(src0)
+    torch.cuda.synchronize()
+    hpk.copy_kernel_tuned(dst.data_ptr(), src.data_ptr(), nbytes,
+                          torch.cuda.current_stream().cuda_stream, unroll, cap)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src0)
+    assert _canaries_intact(base, dst)
+
+
+# The nontemporal streaming kernels (copy, fill, accumulate) cap their grid
+# at 131072 blocks of 256 threads, one 16-byte item per thread per
+# iteration — so they grid-stride only above 512 MiB, the regime of the
+# flagship's 1 GiB D2D copy. This size gives SOME threads (3 blocks + 1) a
+# second iteration, the rest one, plus a 12-byte tail.
+_NT_GRID_CAP = 131072
+_WRAP_NBYTES = _NT_GRID_CAP * 256 * 16 + 16 * (3 * 256 + 1) + 12
+
+
+def test_copy_kernel_grid_stride_wrap(ops, dev):
+    n = _WRAP_NBYTES // 4
+    src = torch.rand(n, device=dev)
+    base, dst = _window(dev, _WRAP_NBYTES, 0, torch.float32)
+    ops.copy_kernel(dst, src)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src)
+    assert _canaries_intact(base, dst)
+
+
+def test_fill_grid_stride_wrap(ops, dev):
+    n = _WRAP_NBYTES // 4
+    base, t = _window(dev, _WRAP_NBYTES, 0, torch.float32)
+    ops.fill(t, -2.25)
+    torch.cuda.synchronize()
+    assert bool((t == -2.25).all())
+    assert t.numel() == n and _canaries_intact(base, t)
+
+
+def test_accumulate_nt_grid_stride_wrap(ops, dev):
+    from hpc_patterns_amd._native import native
+
+    hpk = native()
+    n = _WRAP_NBYTES // 4
+    a0 = torch.rand(n, device=dev)
+    b = torch.rand(n, device=dev)
+    base, a = _window(dev, _WRAP_NBYTES, 0, torch.float32)
+    a.copy_(a0)
+    torch.cuda.synchronize()
+    hpk.acc_f32_nt(a.data_ptr(), b.data_ptr(), n,
+                   torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    a0 += b  # the reference, in place: three 512 MiB buffers, not four
+    assert torch.equal(a, a0)
+    assert _canaries_intact(base, a)
+
+
+# int32 twins (fill_i32 / acc_i32 / reduce_sum_i32): the miniapps' int
+# instantiation, same size, alignment and tail grid as the float kernels.
+
+@pytest.mark.parametrize("n,misalign",
+                         [(n, 4) for n in _MISALIGNED_NS] +
+                         [(n, 0) for n in _TAIL_NS])
+def test_fill_i32(ops, dev, n, misalign):
+    from hpc_patterns_amd._native import native
+
+    base, t = _window(dev, 4 * n, misalign, torch.int32)
+    native().fill_i32(t.data_ptr(), -123456789, n,
+                      torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.equal(t, torch.full((n,), -123456789, dtype=torch.int32,
+                                     device=dev))
+    assert _canaries_intact(base, t)
+
+
+@pytest.mark.parametrize("n,dst_mis,src_mis",
+                         [(n, d, s) for n in _MISALIGNED_NS
+                          for d, s in ((4, 0), (0, 4), (4, 4))] +
+                         [(n, 0, 0) for n in _TAIL_NS])
+def test_acc_i32(ops, dev, n, dst_mis, src_mis):
+    from hpc_patterns_amd._native import native
+
+    g = torch.Generator(device="cpu").manual_seed(n)
+    a0 = torch.randint(-2 ** 30, 2 ** 30, (n,), generator=g,
+                       dtype=torch.int32).to(dev)
+    b0 = torch.randint(-2 ** 30, 2 ** 30, (n,), generator=g,
+                       dtype=torch.int32).to(dev)
+    base, a = _window(dev, 4 * n, dst_mis, torch.int32)
+    _, b = _window(dev, 4 * n, src_mis, torch.int32)
+    a.copy_(a0)
+    b.copy_(b0)
+    torch.cuda.synchronize()
+    native().acc_i32(a.data_ptr(), b.data_ptr(), n,
+                     torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.equal(a, a0 + b0)  # |a0 + b0| < 2^31: no wrap either side
+    assert _canaries_intact(base, a)
+
+
+def test_reduce_sum_i32_needs_64bit_accumulator(ops, dev):
+    from hpc_patterns_amd._native import native
+
+    n = 1 << 20
+    t = torch.full((n,), 2 ** 31 - 1, dtype=torch.int32, device=dev)
+    got = native().reduce_sum_i32(t.data_ptr(), n,
+                                  torch.cuda.current_stream().cuda_stream)
+    assert got == n * (2 ** 31 - 1)
+
+
+@pytest.mark.parametrize("n,misalign", [(1, 0), (1027, 4), ((1 << 20) + 3, 0)])
+def test_reduce_sum_i32_random(ops, dev, n, misalign):
+    from hpc_patterns_amd._native import native
+
+    g = torch.Generator(device="cpu").manual_seed(n)
+    host = torch.randint(-2 ** 30, 2 ** 30 + 1, (n,), generator=g,
+                         dtype=torch.int32)
+    _, t = _window(dev, 4 * n, misalign, torch.int32)
+    t.copy_(host)
+    got = native().reduce_sum_i32(t.data_ptr(), n,
+                                  torch.cuda.current_stream().cuda_stream)
+    assert got == int(host.long().sum())
 
 
 @pytest.mark.parametrize("n", [1, 1000, 1 << 24])
