@@ -9,6 +9,14 @@
 // (tests/test_gpu_kernels.py; every variant at its edge shapes against a
 // float64 reference in tests/test_gpu_gemm_matrix.py) and race-screened.
 //
+// Layout: vector typedefs and the shared device helpers first (tile order,
+// hpk_tile_id, glds16/glds4), then every kernel — all inside the anonymous
+// namespace — then the dispatch table and the five launchers, which name a
+// kernel and its geometry and leave the grid arithmetic to launch_tiled().
+// The kernel bodies still repeat their staging/MFMA/epilogue blocks on
+// purpose: folding them into templates moved register allocation
+// (docs/findings.md #28, profiles/gemm_refactor_ab.md).
+//
 // Members (measured on MI355X, random operands, profiles/gemm_showcase_r2):
 //   k_gemm_bf16_nt<2,2|2,4>   plain two-barrier 128^2 tile; the 8-wave
 //                             64x32 decomposition wins (76 VGPR -> 6
@@ -64,6 +72,10 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+typedef __attribute__((ext_vector_type(16))) int i32x16;
 
 constexpr int BM = 128, BN = 128, BK = 64;
 
@@ -118,6 +130,34 @@ __device__ __forceinline__ int hpk_group_remap(int wg, int tiles_n, int nwg,
   return tm * tiles_n + tn;
 }
 
+// This workgroup's output-tile index: optional bijective 8-XCD round-robin
+// -> tile-linear remap, then the grouped order above. Tile row/col are
+// id / tiles_n and id % tiles_n.
+__device__ __forceinline__ int hpk_tile_id(int tiles_n, int nwg,
+                                           int xcd_swizzle, int group) {
+  int wg = (int)blockIdx.x;
+  if (xcd_swizzle) {
+    int q = nwg / 8, r = nwg % 8;
+    int xcd = wg % 8, i = wg / 8;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
+  }
+  return hpk_group_remap(wg, tiles_n, nwg, group);
+}
+
+// global_load_lds: each lane DMAs 16 B (4 B for the scale rows) from its
+// OWN global address to (wave-uniform LDS base) + lane*size — so `l` is the
+// WAVE chunk base and only `g` is per-lane; LDS images are lane-linear.
+__device__ __forceinline__ void glds16(const void* g, void* l) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void*)g,
+      (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+}
+__device__ __forceinline__ void glds4(const void* g, void* l) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void*)g,
+      (__attribute__((address_space(3))) void*)l, 4, 0, 0);
+}
+
 // Wave-grid decomposition is a template knob: <2,2> = 4 waves of 64x64
 // (4x4 fragments, 190 VGPR+AGPR, 2 waves/SIMD), <2,4> = 8 waves of
 // 64x32 (4x2 fragments, 76 VGPR, 6 waves/SIMD). Measured on MI355X with
@@ -136,14 +176,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_bf16_nt(
   constexpr int WTN = BN / WAVES_N; // wave sub-tile cols
   __shared__ __hip_bfloat16 lds[2 * TILE_HALF]; // [A tile][B tile]
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    // bijective 8-XCD round-robin -> tile-linear remap
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const int tile_m = wg / tiles_n;
   const int tile_n = wg % tiles_n;
   const long brow = (long)tile_m * BM;
@@ -175,13 +208,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_bf16_nt(
       int kk = (int)(o % BK);
       const __hip_bfloat16* ga = A + (brow + row) * (long)K + k0 + kk;
       const __hip_bfloat16* gb = B + (bcol + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(lds + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(lds + TILE_HALF + o_base),
-          16, 0, 0);
+      glds16(ga, lds + o_base);
+      glds16(gb, lds + TILE_HALF + o_base);
     }
     __syncthreads(); // carries vmcnt(0): glds queue drained
 
@@ -235,13 +263,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_bf16_nt_db(
   constexpr int WTN = BN / WAVES_N;
   __shared__ __hip_bfloat16 lds[2 * 2 * TILE_HALF]; // 2 buffers x (A|B)
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * BM;
   const long bcol = (long)(wg % tiles_n) * BN;
   const int tid = threadIdx.x;
@@ -263,13 +285,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_bf16_nt_db(
       int kk = (int)(o % BK);
       const __hip_bfloat16* ga = A + (brow + row) * (long)K + k0 + kk;
       const __hip_bfloat16* gb = B + (bcol + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(dst + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(dst + TILE_HALF + o_base),
-          16, 0, 0);
+      glds16(ga, dst + o_base);
+      glds16(gb, dst + TILE_HALF + o_base);
     }
   };
 
@@ -358,13 +375,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_fp8_nt(
   constexpr int WTN = BN / WAVES_N;
   __shared__ unsigned char lds[2 * TILE_HALF]; // bytes: [A tile][B tile]
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * BM;
   const long bcol = (long)(wg % tiles_n) * BN;
   const int tid = threadIdx.x;
@@ -389,13 +400,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_fp8_nt(
       int kk = (int)(o % BK);
       const unsigned char* ga = A + (brow + row) * (long)K + k0 + kk;
       const unsigned char* gb = B + (bcol + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(lds + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(lds + TILE_HALF + o_base),
-          16, 0, 0);
+      glds16(ga, lds + o_base);
+      glds16(gb, lds + TILE_HALF + o_base);
     }
     __syncthreads();
 
@@ -467,13 +473,7 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_8ph(
     int tiles_n, int nwg, int xcd_swizzle, int group) {
   __shared__ __hip_bfloat16 lds[8 * PHALF]; // 128 KiB
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * 256;
   const long bcol = (long)(wg % tiles_n) * 256;
   const int tid = threadIdx.x;
@@ -504,11 +504,7 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_8ph(
       int row = (int)(o >> 6);
       int kk = (int)(o & 63);
       const __hip_bfloat16* g = G + (rbase + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)g,
-          (__attribute__((address_space(3))) void*)(lds + (long)slot * PHALF +
-                                                    o_base),
-          16, 0, 0);
+      glds16(g, lds + (long)slot * PHALF + o_base);
     }
   };
 
@@ -649,13 +645,7 @@ __global__ __launch_bounds__(512) void k_gemm_fp8_8ph(
     int tiles_n, int nwg, int xcd_swizzle, int group) {
   __shared__ unsigned char lds[8 * PHALF8]; // 64 KiB -> 2 blocks/CU
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * 256;
   const long bcol = (long)(wg % tiles_n) * 256;
   const int tid = threadIdx.x;
@@ -687,11 +677,7 @@ __global__ __launch_bounds__(512) void k_gemm_fp8_8ph(
       int row = (int)(o >> 6);
       int kk = (int)(o & 63);
       const unsigned char* g = G + (rbase + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)g,
-          (__attribute__((address_space(3))) void*)(lds + (long)slot * PHALF8 +
-                                                    o_base),
-          16, 0, 0);
+      glds16(g, lds + (long)slot * PHALF8 + o_base);
     }
   };
 
@@ -851,8 +837,6 @@ __device__ __forceinline__ long mx_unskew(long y) {
   return (row << 7) | ((k - 16 * ((row >> 1) & 5)) & 127);
 }
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
 __global__ __launch_bounds__(512) void k_gemm_mxfp8_nt(
     float* __restrict__ C, const unsigned char* __restrict__ A,
     const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
@@ -862,13 +846,7 @@ __global__ __launch_bounds__(512) void k_gemm_mxfp8_nt(
   // [A data 16K][B data 16K][A scales 512][B scales 512]
   __shared__ unsigned char lds[2 * 128 * MXK + 2 * 512];
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * 128;
   const long bcol = (long)(wg % tiles_n) * 128;
   const int tid = threadIdx.x;
@@ -892,13 +870,8 @@ __global__ __launch_bounds__(512) void k_gemm_mxfp8_nt(
       int kk = (int)(o & 127);
       const unsigned char* ga = A + (brow + row) * (long)K + k0 + kk;
       const unsigned char* gb = B + (bcol + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(lds + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(lds + 128 * MXK + o_base),
-          16, 0, 0);
+      glds16(ga, lds + o_base);
+      glds16(gb, lds + 128 * MXK + o_base);
     }
     // scales: 128 rows x 4 k-blocks per operand; thread t stages one byte
     // of each (ordinary load + ds_write — the barrier drains them anyway)
@@ -923,7 +896,6 @@ __global__ __launch_bounds__(512) void k_gemm_mxfp8_nt(
     const int g = lane >> 4;
     const int kh0 = 64 * (g >> 1) + 16 * (g & 1); // half-0 K byte offset
     const int blk = 2 * (g & 1) + (g >> 1);       // lane's MX block index
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
     auto frag32 = [&](const unsigned char* base, long e) {
       i32x4 lo = *(const i32x4*)__builtin_assume_aligned(
           base + mx_skew(e), 16);
@@ -983,8 +955,6 @@ __device__ __forceinline__ long i8_unskew(long y) {
   return (row << 6) | ((k - 32 * ((row >> 3) & 1)) & 63);
 }
 
-typedef __attribute__((ext_vector_type(4))) int i32x4v;
-
 template <int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_i8_nt(
     int* __restrict__ C, const signed char* __restrict__ A,
@@ -997,13 +967,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_i8_nt(
   constexpr int WTN = BN / WAVES_N;
   __shared__ signed char lds[2 * TILE_HALF]; // bytes: [A tile][B tile]
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * BM;
   const long bcol = (long)(wg % tiles_n) * BN;
   const int tid = threadIdx.x;
@@ -1015,7 +979,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_i8_nt(
   constexpr long bytes_per_issue = (long)THREADS * 16;
   constexpr int ISSUES = TILE_HALF / (THREADS * 16);
   static_assert(ISSUES >= 1, "tile too small");
-  i32x4v acc[MREP][NREP] = {};
+  i32x4 acc[MREP][NREP] = {};
 
   for (int k0 = 0; k0 < K; k0 += BK) {
     __syncthreads();
@@ -1026,26 +990,21 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_i8_nt(
       int kk = (int)(o & 63);
       const signed char* ga = A + (brow + row) * (long)K + k0 + kk;
       const signed char* gb = B + (bcol + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(lds + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(lds + TILE_HALF + o_base),
-          16, 0, 0);
+      glds16(ga, lds + o_base);
+      glds16(gb, lds + TILE_HALF + o_base);
     }
     __syncthreads();
 
     const int kfrag = 16 * (lane >> 4);
-    i32x4v afrag[MREP];
+    i32x4 afrag[MREP];
     for (int m = 0; m < MREP; ++m) {
       int row = wr * WTM + m * 16 + (lane & 15);
-      afrag[m] = *(const i32x4v*)__builtin_assume_aligned(
+      afrag[m] = *(const i32x4*)__builtin_assume_aligned(
           lds + i8_skew(row * BK + kfrag), 16);
     }
     for (int n = 0; n < NREP; ++n) {
       int col = wc * WTN + n * 16 + (lane & 15);
-      i32x4v bfrag = *(const i32x4v*)__builtin_assume_aligned(
+      i32x4 bfrag = *(const i32x4*)__builtin_assume_aligned(
           lds + TILE_HALF + i8_skew(col * BK + kfrag), 16);
       for (int m = 0; m < MREP; ++m)
         acc[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(afrag[m], bfrag,
@@ -1071,7 +1030,6 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_i8_nt(
 // pipeline. The plain two-barrier structure is the right home for the
 // scaled instruction at this tile geometry.
 
-} // namespace
 
 // ---------------------------------------------------------------------------
 // K7-i8-8ph: the deep-pipelined 8-phase schedule at int8 — [128][128]-byte
@@ -1098,13 +1056,7 @@ __global__ __launch_bounds__(512) void k_gemm_i8_8ph(
     int tiles_n, int nwg, int xcd_swizzle, int group) {
   __shared__ signed char lds[8 * PH8I]; // 128 KiB
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * 256;
   const long bcol = (long)(wg % tiles_n) * 256;
   const int tid = threadIdx.x;
@@ -1135,18 +1087,14 @@ __global__ __launch_bounds__(512) void k_gemm_i8_8ph(
       int row = (int)(o >> 7);
       int kk = (int)(o & 127);
       const signed char* g = G + (rbase + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)g,
-          (__attribute__((address_space(3))) void*)(lds + (long)slot * PH8I +
-                                                    o_base),
-          16, 0, 0);
+      glds16(g, lds + (long)slot * PH8I + o_base);
     }
   };
 
-  i32x4v acc[8][4] = {};
-  i32x4v af[4][2];  // current m-group (4 m) x kk
-  i32x4v bl[2][2];  // n0-1 x kk
-  i32x4v bh[2][2];  // n2-3 x kk
+  i32x4 acc[8][4] = {};
+  i32x4 af[4][2];  // current m-group (4 m) x kk
+  i32x4 bl[2][2];  // n0-1 x kk
+  i32x4 bh[2][2];  // n2-3 x kk
 
   const int a_half = 2 + wr;       // this wave's A half id
   const int b_half = wc >> 1;      // this wave's B half id
@@ -1158,21 +1106,21 @@ __global__ __launch_bounds__(512) void k_gemm_i8_8ph(
       for (int k2 = 0; k2 < 2; ++k2) {
         int row = mg * 64 + m * 16 + (lane & 15);
         int kf = k2 * 64 + 16 * (lane >> 4);
-        af[m][k2] = *(const i32x4v*)__builtin_assume_aligned(
+        af[m][k2] = *(const i32x4*)__builtin_assume_aligned(
             sa + i8s_skew(row * 128 + kf), 16);
       }
   };
-  auto read_b = [&](int parity, int ng, i32x4v (*dst)[2]) {
+  auto read_b = [&](int parity, int ng, i32x4 (*dst)[2]) {
     const signed char* sb = lds + (long)(parity * 4 + b_half) * PH8I;
     for (int n = 0; n < 2; ++n)
       for (int k2 = 0; k2 < 2; ++k2) {
         int col = bcol_in_half + (ng * 2 + n) * 16 + (lane & 15);
         int kf = k2 * 64 + 16 * (lane >> 4);
-        dst[n][k2] = *(const i32x4v*)__builtin_assume_aligned(
+        dst[n][k2] = *(const i32x4*)__builtin_assume_aligned(
             sb + i8s_skew(col * 128 + kf), 16);
       }
   };
-  auto mfma16 = [&](int mg, int ng, i32x4v (*bfr)[2]) {
+  auto mfma16 = [&](int mg, int ng, i32x4 (*bfr)[2]) {
     for (int m = 0; m < 4; ++m)
       for (int n = 0; n < 2; ++n)
         for (int k2 = 0; k2 < 2; ++k2)
@@ -1268,11 +1216,6 @@ __global__ __launch_bounds__(512) void k_gemm_i8_8ph(
     }
 }
 
-// Band width (in N-tiles) of the grouped tile order above. Defaults come
-// from interleaved A/B sweeps at 8192^3 and 16384^3 (clock-drift-controlled;
-// docs/gemm.md): row-major is already LLC-friendly up to ~32 N-tiles, wider
-// grids gain 4-7% from 16/32-wide bands. HPK_GEMM_GROUP overrides.
-
 // 256^2-tile 32x32x32 int8 kernel — the fp8 _32 design (see
 // k_gemm_mxfp8_nt_32) at the non-scaled i8 MFMA: per-lane fragment = 16
 // contiguous K elements at k = 16*(lane>>5) of each K-32 step (one
@@ -1286,13 +1229,7 @@ __global__ __launch_bounds__(512) void k_gemm_i8_nt_32(
   constexpr int TILE = 256 * 128; // 32 KiB per operand per buffer (K-128)
   __shared__ unsigned char lds[2 * 2 * TILE];
 
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
   const long brow = (long)(wg / tiles_n) * 256;
   const long bcol = (long)(wg % tiles_n) * 256;
   const int tid = threadIdx.x;
@@ -1301,8 +1238,6 @@ __global__ __launch_bounds__(512) void k_gemm_i8_nt_32(
   const int wr = wid >> 1;
   const int wc = wid & 1;
 
-  typedef __attribute__((ext_vector_type(16))) int i32x16;
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
   i32x16 acc[2][4] = {};
 
   auto stage = [&](int buf, int k0) {
@@ -1315,13 +1250,8 @@ __global__ __launch_bounds__(512) void k_gemm_i8_nt_32(
       int kk = ((p - (row >> 2)) & 7) * 16;
       const signed char* ga = A + (brow + row) * (long)K + k0 + kk;
       const signed char* gb = B + (bcol + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(dst + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(dst + TILE + o_base), 16,
-          0, 0);
+      glds16(ga, dst + o_base);
+      glds16(gb, dst + TILE + o_base);
     }
   };
 
@@ -1378,12 +1308,721 @@ __global__ __launch_bounds__(512) void k_gemm_i8_nt_32(
 }
 
 
-static int gemm_group(int tiles_n) {
-  if (const char* env = std::getenv("HPK_GEMM_GROUP")) return std::atoi(env);
-  if (tiles_n >= 128) return 32;
-  if (tiles_n >= 64) return 16;
-  return 1;
+// ---------------------------------------------------------------------------
+// K7-mxfp4: block-scaled OCP MX-fp4 GEMM — the same scaled MFMA in fp4
+// (e2m1) mode, the 4x-bf16 rate class (~10 PF dense spec; fp4 shares the
+// fp6 rate on CDNA4). fp4_probe2/fp4_probe1 (scripts/probes/) measured a
+// DIAGONAL operand/scale layout — unlike fp8's cross-lane pattern: data
+// lane (row, g) supplies the ONE contiguous OCP 32-block k in
+// [32g, 32g+32) packed 2 elements/byte (within-block nibble order is a
+// free consistent K-permutation — both orders validated), and the lane's
+// OWN scale operand byte 0 (opsel 0) covers exactly that block. Each
+// fragment is therefore ONE contiguous 16-byte LDS read, and the natural
+// [128 rows][64 bytes] tile is bank-conflict-free for the true b128 lane
+// groups (window (4*row + g) mod 32 — enumerated in
+// tests/test_gemm_skew_logic.py): NO skew is needed. Operands live in
+// the low 4 VGPRs of the v8i32 builtin argument (fp4 reads 16 B/lane).
+constexpr int MX4B = 64; // packed bytes per row per K-tile (128 elements)
+__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt(
+    float* __restrict__ C, const unsigned char* __restrict__ A,
+    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
+    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
+    int nwg, int xcd_swizzle, int group) {
+  constexpr int MREP = 4, NREP = 2; // 8 waves as 2x4, 64x32 per wave
+  // [A data 8K][B data 8K][A scales 512][B scales 512]
+  __shared__ unsigned char lds[2 * 128 * MX4B + 2 * 512];
+
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
+  const long brow = (long)(wg / tiles_n) * 128;
+  const long bcol = (long)(wg % tiles_n) * 128;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = wid >> 2;
+  const int wc = wid & 3;
+  const int ks = K / 32;       // scale row stride
+  const long Kb = (long)K / 2; // packed data row stride (bytes)
+
+  unsigned char* sA = lds + 2 * 128 * MX4B;
+  unsigned char* sB = sA + 512;
+  f32x4 acc[MREP][NREP] = {};
+
+  for (int k0 = 0; k0 < K; k0 += 128) {
+    __syncthreads();
+    // data: [128][64] bytes per operand = 512 threads x 16 B, one issue
+    {
+      long o_base = (long)wid * 1024;
+      long o = o_base + (long)lane * 16;
+      int row = (int)(o >> 6);
+      int kk = (int)(o & 63);
+      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
+      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
+      glds16(ga, lds + o_base);
+      glds16(gb, lds + 128 * MX4B + o_base);
+    }
+    // scales: 128 rows x 4 k-blocks per operand (as in the mx8 kernel)
+    {
+      int row = tid >> 2, kb = tid & 3;
+      sA[tid] = As[(brow + row) * (long)ks + k0 / 32 + kb];
+      sB[tid] = Bs[(bcol + row) * (long)ks + k0 / 32 + kb];
+    }
+    __syncthreads();
+
+    const int g = lane >> 4;
+    auto frag16 = [&](const unsigned char* base, long byteoff) {
+      i32x4 lo = *(const i32x4*)__builtin_assume_aligned(base + byteoff, 16);
+      i32x8 f = {};
+      for (int j = 0; j < 4; ++j) f[j] = lo[j];
+      return f;
+    };
+    i32x8 afrag[MREP];
+    int asc[MREP];
+    for (int m = 0; m < MREP; ++m) {
+      int row = wr * 64 + m * 16 + (lane & 15);
+      afrag[m] = frag16(lds, (long)row * MX4B + 16 * g);
+      asc[m] = sA[row * 4 + g];
+    }
+    for (int n = 0; n < NREP; ++n) {
+      int col = wc * 32 + n * 16 + (lane & 15);
+      i32x8 bfrag = frag16(lds + 128 * MX4B, (long)col * MX4B + 16 * g);
+      int bsc = sB[col * 4 + g];
+      for (int m = 0; m < MREP; ++m)
+        acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            afrag[m], bfrag, acc[m][n], 4, 4, 0, asc[m], 0, bsc);
+    }
+  }
+
+  for (int m = 0; m < MREP; ++m)
+    for (int n = 0; n < NREP; ++n) {
+      long row0 = brow + wr * 64 + m * 16 + 4 * (lane >> 4);
+      long col = bcol + wc * 32 + n * 16 + (lane & 15);
+      for (int r = 0; r < 4; ++r)
+        C[(row0 + r) * (long)N + col] = acc[m][n][r];
+    }
 }
+
+
+// 256^2-tile 32x32x64 MX-fp8 kernel — the mx4 _32 design (see
+// k_gemm_mxfp4_nt_32) ported to fp8: same arithmetic-intensity argument
+// (the 128^2 mx8 kernel's 127 FLOP/staged-byte = a ~1 PF naive HBM
+// ceiling, measured 1.4-1.5 PF with LLC help; 256^2 doubles it), same
+// double-buffered all-glds staging. fp8 differences, both measured on
+// hardware (scripts/probes/fp8_probe*_32x32): the operand/scale layout
+// at this shape is HALF-INTERLEAVED, not diagonal — scale lane (row,gs)
+// covers bytes [16gs,+16) of BOTH g-lanes, so half h of lane (row,g)
+// feeds from k [32h + 16g, +16) and the lane passes the scale byte for
+// block g — and the 128-byte rows need a (row>>2)&7 chunk rotation
+// (4 rows share each (8row mod 32) window band; their row>>2 values are
+// distinct mod 8 — enumerated in tests/test_gemm_skew_logic.py).
+// SCALED=false turns it into the plain-fp8 kernel: the scaled MFMA with
+// a hardcoded 127 (= x1.0) scale IS the non-scaled fp8 GEMM, and no
+// 32x32x64 non-scaled fp8 MFMA exists — scale staging drops out
+// entirely (one fewer glds per wave per tile).
+template <bool SCALED>
+__global__ __launch_bounds__(512) void k_gemm_mxfp8_nt_32(
+    float* __restrict__ C, const unsigned char* __restrict__ A,
+    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
+    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
+    int nwg, int xcd_swizzle, int group) {
+  constexpr int TILE = 256 * 128; // 32 KiB per operand per buffer (K-128)
+  __shared__ unsigned char lds[2 * 2 * TILE + 2 * 2048];
+  unsigned char* const sbase = lds + 2 * 2 * TILE;
+
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
+  const long brow = (long)(wg / tiles_n) * 256;
+  const long bcol = (long)(wg % tiles_n) * 256;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = wid >> 1;
+  const int wc = wid & 1;
+  const int ks = K / 32;
+
+  f32x16 acc[2][4] = {};
+
+  auto stage = [&](int buf, int k0) {
+    unsigned char* dst = lds + (long)buf * 2 * TILE;
+    for (int issue = 0; issue < 4; ++issue) {
+      long o_base = (long)issue * 8192 + (long)wid * 1024;
+      long o = o_base + (long)lane * 16;
+      int row = (int)(o >> 7);
+      int p = (int)((o & 127) >> 4);
+      int kk = ((p - (row >> 2)) & 7) * 16;
+      const unsigned char* ga = A + (brow + row) * (long)K + k0 + kk;
+      const unsigned char* gb = B + (bcol + row) * (long)K + k0 + kk;
+      glds16(ga, dst + o_base);
+      glds16(gb, dst + TILE + o_base);
+    }
+    if (SCALED) {
+      const unsigned char* S = (wid < 4) ? As : Bs;
+      long rbase = (wid < 4) ? brow : bcol;
+      int srow = (wid & 3) * 64 + lane;
+      const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
+      unsigned char* sdst =
+          sbase + (long)buf * 2048 + (wid >= 4 ? 1024 : 0) + (wid & 3) * 256;
+      glds4(gs, sdst);
+    }
+  };
+
+  const int g = lane >> 5;
+  const int r31 = lane & 31;
+  int a_off[2], asc_off[2], b_off[4], bsc_off[4];
+  for (int mf = 0; mf < 2; ++mf) {
+    int row = wr * 64 + mf * 32 + r31;
+    a_off[mf] = row * 128;
+    asc_off[mf] = row * 4 + g;
+  }
+  for (int nf = 0; nf < 4; ++nf) {
+    int col = wc * 128 + nf * 32 + r31;
+    b_off[nf] = col * 128;
+    bsc_off[nf] = col * 4 + g;
+  }
+  i32x8 afrag[2];
+  i32x8 bfrag[4];
+
+  stage(0, 0);
+  for (int k0 = 0; k0 < K; k0 += 128) {
+    const int cur = (k0 >> 7) & 1;
+    const bool more = (k0 + 128) < K;
+    if (more) stage(cur ^ 1, k0 + 128);
+    if (more)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(SCALED ? 9 : 8) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    const unsigned char* la = lds + (long)cur * 2 * TILE;
+    const unsigned char* lb = la + TILE;
+    const unsigned char* sA = sbase + (long)cur * 2048;
+    const unsigned char* sB = sA + 1024;
+    for (int kk = 0; kk < 2; ++kk) {
+      int asc[2];
+      for (int mf = 0; mf < 2; ++mf) {
+        int row = wr * 64 + mf * 32 + r31;
+        int rot = row >> 2;
+        int ch0 = (4 * kk + g + rot) & 7;      // half h=0
+        int ch1 = (4 * kk + 2 + g + rot) & 7;  // half h=1
+        *(i32x4*)&afrag[mf] = *(const i32x4*)__builtin_assume_aligned(
+            la + a_off[mf] + 16 * ch0, 16);
+        *((i32x4*)&afrag[mf] + 1) = *(const i32x4*)__builtin_assume_aligned(
+            la + a_off[mf] + 16 * ch1, 16);
+        asc[mf] = SCALED ? sA[asc_off[mf] + 2 * kk] : 127;
+      }
+      for (int nf = 0; nf < 4; ++nf) {
+        int col = wc * 128 + nf * 32 + r31;
+        int rot = col >> 2;
+        int ch0 = (4 * kk + g + rot) & 7;
+        int ch1 = (4 * kk + 2 + g + rot) & 7;
+        *(i32x4*)&bfrag[nf] = *(const i32x4*)__builtin_assume_aligned(
+            lb + b_off[nf] + 16 * ch0, 16);
+        *((i32x4*)&bfrag[nf] + 1) = *(const i32x4*)__builtin_assume_aligned(
+            lb + b_off[nf] + 16 * ch1, 16);
+        int bsc = SCALED ? sB[bsc_off[nf] + 2 * kk] : 127;
+        for (int mf = 0; mf < 2; ++mf)
+          acc[mf][nf] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+              afrag[mf], bfrag[nf], acc[mf][nf], 0, 0, 0, asc[mf], 0, bsc);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+
+  for (int mf = 0; mf < 2; ++mf)
+    for (int nf = 0; nf < 4; ++nf) {
+      long col = bcol + wc * 128 + nf * 32 + r31;
+      for (int r = 0; r < 16; ++r) {
+        long row = brow + wr * 64 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+        C[row * (long)N + col] = acc[mf][nf][r];
+      }
+    }
+}
+
+
+// 4-wave variant: same diagonal-layout staging, 64x64 per wave (MREP =
+// NREP = 4) — 16 MFMAs per wave per K-tile instead of 8, halving the
+// relative cost of the per-tile barrier + staging-drain stall that PMC
+// shows dominating the 8-wave kernel (MfmaUtil 20.6%). HPK_MX4_WAVES
+// selects; the launcher defaults to the measured winner.
+__global__ __launch_bounds__(256) void k_gemm_mxfp4_nt_w4(
+    float* __restrict__ C, const unsigned char* __restrict__ A,
+    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
+    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
+    int nwg, int xcd_swizzle, int group) {
+  constexpr int MREP = 4, NREP = 4; // 4 waves as 2x2, 64x64 per wave
+  __shared__ unsigned char lds[2 * 128 * MX4B + 2 * 512];
+
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
+  const long brow = (long)(wg / tiles_n) * 128;
+  const long bcol = (long)(wg % tiles_n) * 128;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = wid >> 1;
+  const int wc = wid & 1;
+  const int ks = K / 32;
+  const long Kb = (long)K / 2;
+
+  unsigned char* sA = lds + 2 * 128 * MX4B;
+  unsigned char* sB = sA + 512;
+  f32x4 acc[MREP][NREP] = {};
+
+  for (int k0 = 0; k0 < K; k0 += 128) {
+    __syncthreads();
+    // data: [128][64] bytes per operand = 256 threads x 16 B x 2 issues
+    for (int issue = 0; issue < 2; ++issue) {
+      long o_base = (long)issue * 4096 + (long)wid * 1024;
+      long o = o_base + (long)lane * 16;
+      int row = (int)(o >> 6);
+      int kk = (int)(o & 63);
+      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
+      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
+      glds16(ga, lds + o_base);
+      glds16(gb, lds + 128 * MX4B + o_base);
+    }
+    // scales: 512 entries per operand, 2 per thread
+    {
+      int e0 = tid * 2;
+      int row = e0 >> 2, kb = e0 & 3;
+      sA[e0] = As[(brow + row) * (long)ks + k0 / 32 + kb];
+      sB[e0] = Bs[(bcol + row) * (long)ks + k0 / 32 + kb];
+      int e1 = e0 + 1;
+      int row1 = e1 >> 2, kb1 = e1 & 3;
+      sA[e1] = As[(brow + row1) * (long)ks + k0 / 32 + kb1];
+      sB[e1] = Bs[(bcol + row1) * (long)ks + k0 / 32 + kb1];
+    }
+    __syncthreads();
+
+    const int g = lane >> 4;
+    auto frag16 = [&](const unsigned char* base, long byteoff) {
+      i32x4 lo = *(const i32x4*)__builtin_assume_aligned(base + byteoff, 16);
+      i32x8 f = {};
+      for (int j = 0; j < 4; ++j) f[j] = lo[j];
+      return f;
+    };
+    i32x8 afrag[MREP];
+    int asc[MREP];
+    for (int m = 0; m < MREP; ++m) {
+      int row = wr * 64 + m * 16 + (lane & 15);
+      afrag[m] = frag16(lds, (long)row * MX4B + 16 * g);
+      asc[m] = sA[row * 4 + g];
+    }
+    for (int n = 0; n < NREP; ++n) {
+      int col = wc * 64 + n * 16 + (lane & 15);
+      i32x8 bfrag = frag16(lds + 128 * MX4B, (long)col * MX4B + 16 * g);
+      int bsc = sB[col * 4 + g];
+      for (int m = 0; m < MREP; ++m)
+        acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            afrag[m], bfrag, acc[m][n], 4, 4, 0, asc[m], 0, bsc);
+    }
+  }
+
+  for (int m = 0; m < MREP; ++m)
+    for (int n = 0; n < NREP; ++n) {
+      long row0 = brow + wr * 64 + m * 16 + 4 * (lane >> 4);
+      long col = bcol + wc * 64 + n * 16 + (lane & 15);
+      for (int r = 0; r < 4; ++r)
+        C[(row0 + r) * (long)N + col] = acc[m][n][r];
+    }
+}
+
+
+// Double-buffered variant: tile t+1's staging DMAs issue before tile t's
+// compute and a counted s_waitcnt retires exactly tile t's (the bf16 db
+// discipline, findings #18). ALL staging is global_load_lds — including
+// the scales, gathered as 4-byte dwords by waves 0-3 (K % 128 makes the
+// scale rows dword-aligned) — so the per-wave vmcnt count is exact
+// (3 issues for waves 0-3, 2 for waves 4-7; mixing ordinary loads into
+// the queue would break the count — the guide's load-kind trap). PMC
+// motivation: the plain kernel's MfmaUtil is 20.6% — each tile eats a
+// full memory latency inside the barrier window; with 34 KiB LDS and 85
+// VGPRs two 8-wave blocks stay resident on top of the intra-block
+// prefetch. HPK_MX4_WAVES=db selects... (launcher: HPK_GEMM_VARIANT
+// conventions kept: default is the measured winner).
+__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt_db(
+    float* __restrict__ C, const unsigned char* __restrict__ A,
+    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
+    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
+    int nwg, int xcd_swizzle, int group) {
+  constexpr int MREP = 4, NREP = 2;
+  constexpr int TILE = 128 * MX4B; // 8 KiB per operand per buffer
+  // ONE shared array (a second __shared__ object would force vmcnt(0)
+  // before every ds_read): [buf][A|B data] x2, then [buf][sA|sB] x2
+  __shared__ unsigned char lds[2 * 2 * TILE + 2 * 1024];
+  unsigned char* const sbase = lds + 2 * 2 * TILE;
+
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
+  const long brow = (long)(wg / tiles_n) * 128;
+  const long bcol = (long)(wg % tiles_n) * 128;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = wid >> 2;
+  const int wc = wid & 3;
+  const int ks = K / 32;
+  const long Kb = (long)K / 2;
+
+  f32x4 acc[MREP][NREP] = {};
+
+  auto stage = [&](int buf, int k0) {
+    unsigned char* dst = lds + (long)buf * 2 * TILE;
+    long o_base = (long)wid * 1024;
+    long o = o_base + (long)lane * 16;
+    int row = (int)(o >> 6);
+    int kk = (int)(o & 63);
+    const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
+    const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
+    glds16(ga, dst + o_base);
+    glds16(gb, dst + TILE + o_base);
+    if (wid < 4) {
+      // scale dwords: wave w, lane l gathers rows (w&1)*64+l of As (w<2)
+      // or Bs — dest layout stays s[row*4 + kb]
+      const unsigned char* S = (wid < 2) ? As : Bs;
+      long rbase = (wid < 2) ? brow : bcol;
+      int srow = (wid & 1) * 64 + lane;
+      const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
+      unsigned char* sdst =
+          sbase + (long)buf * 1024 + (wid >= 2 ? 512 : 0) + (wid & 1) * 256;
+      glds4(gs, sdst);
+    }
+  };
+
+  // VALU-diet (PMC showed 4 VALU per MFMA on the lambda version):
+  // per-lane LDS byte offsets are K-invariant — compute once; operand
+  // i32x8s persist across the loop so their top halves (unused in fp4
+  // mode) stay zero with no per-tile re-init/copies.
+  const int g = lane >> 4;
+  int a_off[MREP], asc_off[MREP], b_off[NREP], bsc_off[NREP];
+  for (int m = 0; m < MREP; ++m) {
+    int row = wr * 64 + m * 16 + (lane & 15);
+    a_off[m] = row * MX4B + 16 * g;
+    asc_off[m] = row * 4 + g;
+  }
+  for (int n = 0; n < NREP; ++n) {
+    int col = wc * 32 + n * 16 + (lane & 15);
+    b_off[n] = col * MX4B + 16 * g;
+    bsc_off[n] = col * 4 + g;
+  }
+  i32x8 afrag[MREP] = {};
+  i32x8 bfrag[NREP] = {};
+
+  stage(0, 0);
+  for (int k0 = 0; k0 < K; k0 += 128) {
+    const int cur = (k0 >> 7) & 1;
+    const bool more = (k0 + 128) < K;
+    if (more) stage(cur ^ 1, k0 + 128);
+    if (more) {
+      if (wid < 4)
+        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    const unsigned char* la = lds + (long)cur * 2 * TILE;
+    const unsigned char* lb = la + TILE;
+    const unsigned char* sA = sbase + (long)cur * 1024;
+    const unsigned char* sB = sA + 512;
+    int asc[MREP];
+    for (int m = 0; m < MREP; ++m) {
+      *(i32x4*)&afrag[m] = *(const i32x4*)__builtin_assume_aligned(
+          la + a_off[m], 16);
+      asc[m] = sA[asc_off[m]];
+    }
+    for (int n = 0; n < NREP; ++n) {
+      *(i32x4*)&bfrag[n] = *(const i32x4*)__builtin_assume_aligned(
+          lb + b_off[n], 16);
+      int bsc = sB[bsc_off[n]];
+      for (int m = 0; m < MREP; ++m)
+        acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            afrag[m], bfrag[n], acc[m][n], 4, 4, 0, asc[m], 0, bsc);
+    }
+    // all waves done reading buf[cur] before the next prefetch overwrites
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+
+  for (int m = 0; m < MREP; ++m)
+    for (int n = 0; n < NREP; ++n) {
+      long row0 = brow + wr * 64 + m * 16 + 4 * (lane >> 4);
+      long col = bcol + wc * 32 + n * 16 + (lane & 15);
+      for (int r = 0; r < 4; ++r)
+        C[(row0 + r) * (long)N + col] = acc[m][n][r];
+    }
+}
+
+
+// 32x32x64 variant at a 256^2 tile: the bigger scaled MFMA
+// (mfma_scale_f32_32x32x64_f8f6f4, 9099 TF ubench) plus the bigger tile
+// attack the two measured walls in order: an un-skewed 64-byte-stride
+// tile read 8-way bank conflicts (SQ_LDS_BANK_CONFLICT = 4x MFMA count,
+// fixed by the (row>>3)&3 chunk rotation below), and the 128^2 tile's
+// arithmetic intensity (254 FLOP/staged-byte = a ~2.0 PF HBM ceiling at
+// 8 TB/s — the measured 2.0-2.1 PF plateau of ALL 128^2 fp4 variants).
+// 256^2 doubles intensity (508 FLOP/B -> ~4 PF ceiling). fp4_probe3
+// measured the same DIAGONAL operand/scale layout at this shape: lane
+// (row=lane&31, g=lane>>5) supplies OCP block k in [32g,32g+32),
+// own-lane scale byte. 8 waves as 4x2 (64x128 per wave, 16 MFMAs per
+// K-128 tile), f32x16 accumulators (128 AGPRs), double-buffered
+// all-glds staging (scale rows as size-4 glds: sub-dword glds lands in
+// 4-byte-per-lane LDS slots — measured, and a K-128 tile's 4 scale
+// bytes fill the slot exactly).
+__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt_32(
+    float* __restrict__ C, const unsigned char* __restrict__ A,
+    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
+    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
+    int nwg, int xcd_swizzle, int group) {
+  constexpr int TILE = 256 * 64; // 16 KiB per operand per buffer (K-128)
+  __shared__ unsigned char lds[2 * 2 * TILE + 2 * 2048];
+  unsigned char* const sbase = lds + 2 * 2 * TILE;
+
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
+  const long brow = (long)(wg / tiles_n) * 256;
+  const long bcol = (long)(wg % tiles_n) * 256;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = wid >> 1; // 4 wave-rows of 64
+  const int wc = wid & 1;  // 2 wave-cols of 128
+  const int ks = K / 32;
+  const long Kb = (long)K / 2;
+
+  f32x16 acc[2][4] = {};
+
+  auto stage = [&](int buf, int k0) {
+    unsigned char* dst = lds + (long)buf * 2 * TILE;
+    // anti-bank-conflict chunk rotation: LDS chunk position p of row r
+    // holds global chunk (p - (r>>3)) & 3 (true-lane-group enumeration
+    // in tests/test_gemm_skew_logic.py); glds keeps LDS lane-linear so
+    // the rotation is applied to the SOURCE chunk address
+    for (int issue = 0; issue < 2; ++issue) {
+      long o_base = (long)issue * 8192 + (long)wid * 1024;
+      long o = o_base + (long)lane * 16;
+      int row = (int)(o >> 6);
+      int p = (int)((o & 63) >> 4);
+      int kk = ((p - (row >> 3)) & 3) * 16;
+      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
+      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
+      glds16(ga, dst + o_base);
+      glds16(gb, dst + TILE + o_base);
+    }
+    // scales: one dword per row (K-128 tile = 4 e8m0 bytes); waves 0-3
+    // gather As rows wid*64+lane, waves 4-7 Bs
+    const unsigned char* S = (wid < 4) ? As : Bs;
+    long rbase = (wid < 4) ? brow : bcol;
+    int srow = (wid & 3) * 64 + lane;
+    const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
+    unsigned char* sdst =
+        sbase + (long)buf * 2048 + (wid >= 4 ? 1024 : 0) + (wid & 3) * 256;
+    glds4(gs, sdst);
+  };
+
+  // K-invariant per-lane offsets
+  const int g = lane >> 5;
+  const int r31 = lane & 31;
+  int a_off[2], asc_off[2], b_off[4], bsc_off[4];
+  for (int mf = 0; mf < 2; ++mf) {
+    int row = wr * 64 + mf * 32 + r31;
+    a_off[mf] = row * 64;
+    asc_off[mf] = row * 4 + g;
+  }
+  for (int nf = 0; nf < 4; ++nf) {
+    int col = wc * 128 + nf * 32 + r31;
+    b_off[nf] = col * 64;
+    bsc_off[nf] = col * 4 + g;
+  }
+  i32x8 afrag[2] = {};
+  i32x8 bfrag[4] = {};
+
+  stage(0, 0);
+  for (int k0 = 0; k0 < K; k0 += 128) {
+    const int cur = (k0 >> 7) & 1;
+    const bool more = (k0 + 128) < K;
+    if (more) stage(cur ^ 1, k0 + 128);
+    if (more)
+      asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    const unsigned char* la = lds + (long)cur * 2 * TILE;
+    const unsigned char* lb = la + TILE;
+    const unsigned char* sA = sbase + (long)cur * 2048;
+    const unsigned char* sB = sA + 1024;
+    for (int kk = 0; kk < 2; ++kk) {
+      int asc[2];
+      for (int mf = 0; mf < 2; ++mf) {
+        int row = wr * 64 + mf * 32 + r31;
+        int ch = (g + 2 * kk + (row >> 3)) & 3;
+        *(i32x4*)&afrag[mf] = *(const i32x4*)__builtin_assume_aligned(
+            la + a_off[mf] + 16 * ch, 16);
+        asc[mf] = sA[asc_off[mf] + 2 * kk];
+      }
+      for (int nf = 0; nf < 4; ++nf) {
+        int col = wc * 128 + nf * 32 + r31;
+        int ch = (g + 2 * kk + (col >> 3)) & 3;
+        *(i32x4*)&bfrag[nf] = *(const i32x4*)__builtin_assume_aligned(
+            lb + b_off[nf] + 16 * ch, 16);
+        int bsc = sB[bsc_off[nf] + 2 * kk];
+        for (int mf = 0; mf < 2; ++mf)
+          acc[mf][nf] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+              afrag[mf], bfrag[nf], acc[mf][nf], 4, 4, 0, asc[mf], 0, bsc);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+
+  for (int mf = 0; mf < 2; ++mf)
+    for (int nf = 0; nf < 4; ++nf) {
+      long col = bcol + wc * 128 + nf * 32 + r31;
+      for (int r = 0; r < 16; ++r) {
+        long row = brow + wr * 64 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+        C[row * (long)N + col] = acc[mf][nf][r];
+      }
+    }
+}
+
+
+// 256x128-tile variant of the 32x32x64 mx4 kernel: the occupancy
+// experiment the final PMC motivates (181 VGPR x 2 waves/SIMD = one
+// resident block; nothing covers the barrier windows, MfmaUtil 35%).
+// Halving the N-tile drops the accumulator floor to 64 VGPRs/lane so
+// TWO 8-wave blocks co-reside (4 waves/SIMD) and cover each other's
+// waits — at the price of arithmetic intensity (341 vs 508
+// FLOP/staged-byte). 8 waves as 4x2 of 64x64; per-wave glds counts
+// differ (A 2 issues + B 1 for all waves, + 1 scale issue for waves
+// 0-5), so the counted vmcnt branches per wave.
+__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt_32h(
+    float* __restrict__ C, const unsigned char* __restrict__ A,
+    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
+    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
+    int nwg, int xcd_swizzle, int group) {
+  constexpr int ATILE = 256 * 64; // 16 KiB
+  constexpr int BTILE = 128 * 64; // 8 KiB
+  __shared__ unsigned char lds[2 * (ATILE + BTILE) + 2 * 1536];
+  unsigned char* const sbase = lds + 2 * (ATILE + BTILE);
+
+  const int wg = hpk_tile_id(tiles_n, nwg, xcd_swizzle, group);
+  const long brow = (long)(wg / tiles_n) * 256;
+  const long bcol = (long)(wg % tiles_n) * 128;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = wid >> 1; // 4 wave-rows of 64
+  const int wc = wid & 1;  // 2 wave-cols of 64
+  const int ks = K / 32;
+  const long Kb = (long)K / 2;
+
+  f32x16 acc[2][2] = {};
+
+  auto stage = [&](int buf, int k0) {
+    unsigned char* dst = lds + (long)buf * (ATILE + BTILE);
+    for (int issue = 0; issue < 2; ++issue) { // A: 256 rows
+      long o_base = (long)issue * 8192 + (long)wid * 1024;
+      long o = o_base + (long)lane * 16;
+      int row = (int)(o >> 6);
+      int p = (int)((o & 63) >> 4);
+      int kk = ((p - (row >> 3)) & 3) * 16;
+      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
+      glds16(ga, dst + o_base);
+    }
+    { // B: 128 rows, one issue
+      long o_base = (long)wid * 1024;
+      long o = o_base + (long)lane * 16;
+      int row = (int)(o >> 6);
+      int p = (int)((o & 63) >> 4);
+      int kk = ((p - (row >> 3)) & 3) * 16;
+      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
+      glds16(gb, dst + ATILE + o_base);
+    }
+    if (wid < 6) { // scales: A rows 0-255 (waves 0-3), B rows 0-127 (4-5)
+      const unsigned char* S = (wid < 4) ? As : Bs;
+      long rbase = (wid < 4) ? brow : bcol;
+      int srow = (wid < 4 ? (wid & 3) : (wid & 1)) * 64 + lane;
+      const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
+      unsigned char* sdst = sbase + (long)buf * 1536 +
+                            (wid < 4 ? (wid & 3) * 256 : 1024 + (wid & 1) * 256);
+      glds4(gs, sdst);
+    }
+  };
+
+  const int g = lane >> 5;
+  const int r31 = lane & 31;
+  int a_off[2], asc_off[2], b_off[2], bsc_off[2];
+  for (int mf = 0; mf < 2; ++mf) {
+    int row = wr * 64 + mf * 32 + r31;
+    a_off[mf] = row * 64;
+    asc_off[mf] = row * 4 + g;
+  }
+  for (int nf = 0; nf < 2; ++nf) {
+    int col = wc * 64 + nf * 32 + r31;
+    b_off[nf] = col * 64;
+    bsc_off[nf] = col * 4 + g;
+  }
+  i32x8 afrag[2] = {};
+  i32x8 bfrag[2] = {};
+
+  stage(0, 0);
+  for (int k0 = 0; k0 < K; k0 += 128) {
+    const int cur = (k0 >> 7) & 1;
+    const bool more = (k0 + 128) < K;
+    if (more) stage(cur ^ 1, k0 + 128);
+    if (more) {
+      if (wid < 6)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    const unsigned char* la = lds + (long)cur * (ATILE + BTILE);
+    const unsigned char* lb = la + ATILE;
+    const unsigned char* sA = sbase + (long)cur * 1536;
+    const unsigned char* sB = sA + 1024;
+    for (int kk = 0; kk < 2; ++kk) {
+      int asc[2];
+      for (int mf = 0; mf < 2; ++mf) {
+        int row = wr * 64 + mf * 32 + r31;
+        int ch = (g + 2 * kk + (row >> 3)) & 3;
+        *(i32x4*)&afrag[mf] = *(const i32x4*)__builtin_assume_aligned(
+            la + a_off[mf] + 16 * ch, 16);
+        asc[mf] = sA[asc_off[mf] + 2 * kk];
+      }
+      for (int nf = 0; nf < 2; ++nf) {
+        int col = wc * 64 + nf * 32 + r31;
+        int ch = (g + 2 * kk + (col >> 3)) & 3;
+        *(i32x4*)&bfrag[nf] = *(const i32x4*)__builtin_assume_aligned(
+            lb + b_off[nf] + 16 * ch, 16);
+        int bsc = sB[bsc_off[nf] + 2 * kk];
+        for (int mf = 0; mf < 2; ++mf)
+          acc[mf][nf] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+              afrag[mf], bfrag[nf], acc[mf][nf], 4, 4, 0, asc[mf], 0, bsc);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+
+  for (int mf = 0; mf < 2; ++mf)
+    for (int nf = 0; nf < 2; ++nf) {
+      long col = bcol + wc * 64 + nf * 32 + r31;
+      for (int r = 0; r < 16; ++r) {
+        long row = brow + wr * 64 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+        C[row * (long)N + col] = acc[mf][nf][r];
+      }
+    }
+}
+
+
+} // namespace
 
 // ---------------------------------------------------------------------------
 // Dispatch: ONE place decides which kernel a (kind, shape, HPK_* env)
@@ -1487,6 +2126,18 @@ const char* gemm_variant_name(const char* kind, long M, long N, long K) {
   return kGemmVariantNames[(int)gemm_variant_id(kind ? kind : "", M, N, K)];
 }
 
+// Band width (in N-tiles) of the grouped tile order (hpk_group_remap).
+// Defaults come from interleaved A/B sweeps at 8192^3 and 16384^3
+// (clock-drift-controlled; docs/gemm.md): row-major is already
+// LLC-friendly up to ~32 N-tiles, wider grids gain 4-7% from 16/32-wide
+// bands. HPK_GEMM_GROUP overrides.
+static int gemm_group(int tiles_n) {
+  if (const char* env = std::getenv("HPK_GEMM_GROUP")) return std::atoi(env);
+  if (tiles_n >= 128) return 32;
+  if (tiles_n >= 64) return 16;
+  return 1;
+}
+
 // tile order of the 256^2 / 256x128 "32" kernels: row-major unless
 // HPK_GEMM_GROUP is set (measured, 16384^3 interleaved sweep: row-major
 // beats 16/32-wide bands — one resident block/CU makes the concurrent
@@ -1496,986 +2147,143 @@ static int gemm_group32() {
   return genv ? std::atoi(genv) : 1;
 }
 
-void launch_gemm_i8_nt(int* C, const void* A, const void* B, long M,
-                       long N, long K, hipStream_t stream, int xcd_swizzle) {
-  const GemmVariant var = gemm_variant_id("i8", M, N, K);
+// One launch of a tiled GEMM kernel: the grid is one workgroup per
+// tile_m x tile_n output tile; `ptrs` are the kernel's leading pointer
+// arguments (C, A, B[, As, Bs]).
+struct GemmCall {
+  long M, N, K;
+  hipStream_t stream;
+  int xcd_swizzle;
+};
+template <class Kern, class... Ptrs>
+static void launch_tiled(Kern kern, const char* label, int tile_m, int tile_n,
+                         int threads, int group, const GemmCall& g,
+                         Ptrs... ptrs) {
+  const int tiles_n = (int)(g.N / tile_n);
+  const int nwg = (int)(g.M / tile_m) * tiles_n;
+  hipLaunchKernelGGL(kern, dim3(nwg), dim3(threads), 0, g.stream, ptrs...,
+                     (int)g.M, (int)g.N, (int)g.K, tiles_n, nwg,
+                     g.xcd_swizzle, group);
+  check_hip(hipGetLastError(), label);
+}
+
+// NOTE: the bf16, fp8 and i8 launchers derive the band width from N / 256
+// even when a 128-tile kernel runs (whose grid has N / 128 tile columns).
+// That is how the defaults were measured; "fixing" it changes tile order
+// and speed, so it stays.
+
+void launch_gemm_bf16_nt(float* C, const void* A, const void* B, long M,
+                         long N, long K, hipStream_t stream,
+                         int xcd_swizzle) {
+  const GemmCall g{M, N, K, stream, xcd_swizzle};
+  const __hip_bfloat16* a = (const __hip_bfloat16*)A;
+  const __hip_bfloat16* b = (const __hip_bfloat16*)B;
   const int grp = gemm_group((int)(N / 256));
-  const signed char* a = (const signed char*)A;
-  const signed char* b = (const signed char*)B;
-  switch (var) {
-  case GemmVariant::i8_32: {
-    int tn32 = (int)(N / 256);
-    int n32 = (int)(M / 256) * tn32;
-    hipLaunchKernelGGL(k_gemm_i8_nt_32, dim3(n32), dim3(512), 0, stream, C,
-                       a, b, (int)M, (int)N, (int)K, tn32, n32, xcd_swizzle,
-                       gemm_group32());
-    check_hip(hipGetLastError(), "launch_gemm_i8_nt(32)");
-    return;
-  }
-  case GemmVariant::i8_8ph: {
-    int tn = (int)(N / 256);
-    int n8 = (int)(M / 256) * tn;
-    hipLaunchKernelGGL(k_gemm_i8_8ph, dim3(n8), dim3(512), 0, stream, C, a,
-                       b, (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
-    check_hip(hipGetLastError(), "launch_gemm_i8_nt(8ph)");
-    return;
-  }
-  default: {
-    int tiles_n = (int)(N / BN);
-    int nwg = (int)(M / BM) * tiles_n;
-    hipLaunchKernelGGL((k_gemm_i8_nt<2, 4>), dim3(nwg), dim3(512), 0, stream,
-                       C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
-    check_hip(hipGetLastError(), "launch_gemm_i8_nt");
-  }
-  }
-}
-
-
-// ---------------------------------------------------------------------------
-// K7-mxfp4: block-scaled OCP MX-fp4 GEMM — the same scaled MFMA in fp4
-// (e2m1) mode, the 4x-bf16 rate class (~10 PF dense spec; fp4 shares the
-// fp6 rate on CDNA4). fp4_probe2/fp4_probe1 (scripts/probes/) measured a
-// DIAGONAL operand/scale layout — unlike fp8's cross-lane pattern: data
-// lane (row, g) supplies the ONE contiguous OCP 32-block k in
-// [32g, 32g+32) packed 2 elements/byte (within-block nibble order is a
-// free consistent K-permutation — both orders validated), and the lane's
-// OWN scale operand byte 0 (opsel 0) covers exactly that block. Each
-// fragment is therefore ONE contiguous 16-byte LDS read, and the natural
-// [128 rows][64 bytes] tile is bank-conflict-free for the true b128 lane
-// groups (window (4*row + g) mod 32 — enumerated in
-// tests/test_gemm_skew_logic.py): NO skew is needed. Operands live in
-// the low 4 VGPRs of the v8i32 builtin argument (fp4 reads 16 B/lane).
-constexpr int MX4B = 64; // packed bytes per row per K-tile (128 elements)
-__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt(
-    float* __restrict__ C, const unsigned char* __restrict__ A,
-    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
-    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
-    int nwg, int xcd_swizzle, int group) {
-  constexpr int MREP = 4, NREP = 2; // 8 waves as 2x4, 64x32 per wave
-  // [A data 8K][B data 8K][A scales 512][B scales 512]
-  __shared__ unsigned char lds[2 * 128 * MX4B + 2 * 512];
-
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
-  const long brow = (long)(wg / tiles_n) * 128;
-  const long bcol = (long)(wg % tiles_n) * 128;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid >> 2;
-  const int wc = wid & 3;
-  const int ks = K / 32;       // scale row stride
-  const long Kb = (long)K / 2; // packed data row stride (bytes)
-
-  unsigned char* sA = lds + 2 * 128 * MX4B;
-  unsigned char* sB = sA + 512;
-  f32x4 acc[MREP][NREP] = {};
-
-  for (int k0 = 0; k0 < K; k0 += 128) {
-    __syncthreads();
-    // data: [128][64] bytes per operand = 512 threads x 16 B, one issue
-    {
-      long o_base = (long)wid * 1024;
-      long o = o_base + (long)lane * 16;
-      int row = (int)(o >> 6);
-      int kk = (int)(o & 63);
-      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
-      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(lds + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(lds + 128 * MX4B + o_base),
-          16, 0, 0);
-    }
-    // scales: 128 rows x 4 k-blocks per operand (as in the mx8 kernel)
-    {
-      int row = tid >> 2, kb = tid & 3;
-      sA[tid] = As[(brow + row) * (long)ks + k0 / 32 + kb];
-      sB[tid] = Bs[(bcol + row) * (long)ks + k0 / 32 + kb];
-    }
-    __syncthreads();
-
-    const int g = lane >> 4;
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
-    auto frag16 = [&](const unsigned char* base, long byteoff) {
-      i32x4 lo = *(const i32x4*)__builtin_assume_aligned(base + byteoff, 16);
-      i32x8 f = {};
-      for (int j = 0; j < 4; ++j) f[j] = lo[j];
-      return f;
-    };
-    i32x8 afrag[MREP];
-    int asc[MREP];
-    for (int m = 0; m < MREP; ++m) {
-      int row = wr * 64 + m * 16 + (lane & 15);
-      afrag[m] = frag16(lds, (long)row * MX4B + 16 * g);
-      asc[m] = sA[row * 4 + g];
-    }
-    for (int n = 0; n < NREP; ++n) {
-      int col = wc * 32 + n * 16 + (lane & 15);
-      i32x8 bfrag = frag16(lds + 128 * MX4B, (long)col * MX4B + 16 * g);
-      int bsc = sB[col * 4 + g];
-      for (int m = 0; m < MREP; ++m)
-        acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            afrag[m], bfrag, acc[m][n], 4, 4, 0, asc[m], 0, bsc);
-    }
-  }
-
-  for (int m = 0; m < MREP; ++m)
-    for (int n = 0; n < NREP; ++n) {
-      long row0 = brow + wr * 64 + m * 16 + 4 * (lane >> 4);
-      long col = bcol + wc * 32 + n * 16 + (lane & 15);
-      for (int r = 0; r < 4; ++r)
-        C[(row0 + r) * (long)N + col] = acc[m][n][r];
-    }
-}
-
-
-// 256^2-tile 32x32x64 MX-fp8 kernel — the mx4 _32 design (see
-// k_gemm_mxfp4_nt_32) ported to fp8: same arithmetic-intensity argument
-// (the 128^2 mx8 kernel's 127 FLOP/staged-byte = a ~1 PF naive HBM
-// ceiling, measured 1.4-1.5 PF with LLC help; 256^2 doubles it), same
-// double-buffered all-glds staging. fp8 differences, both measured on
-// hardware (scripts/probes/fp8_probe*_32x32): the operand/scale layout
-// at this shape is HALF-INTERLEAVED, not diagonal — scale lane (row,gs)
-// covers bytes [16gs,+16) of BOTH g-lanes, so half h of lane (row,g)
-// feeds from k [32h + 16g, +16) and the lane passes the scale byte for
-// block g — and the 128-byte rows need a (row>>2)&7 chunk rotation
-// (4 rows share each (8row mod 32) window band; their row>>2 values are
-// distinct mod 8 — enumerated in tests/test_gemm_skew_logic.py).
-// SCALED=false turns it into the plain-fp8 kernel: the scaled MFMA with
-// a hardcoded 127 (= x1.0) scale IS the non-scaled fp8 GEMM, and no
-// 32x32x64 non-scaled fp8 MFMA exists — scale staging drops out
-// entirely (one fewer glds per wave per tile).
-template <bool SCALED>
-__global__ __launch_bounds__(512) void k_gemm_mxfp8_nt_32(
-    float* __restrict__ C, const unsigned char* __restrict__ A,
-    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
-    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
-    int nwg, int xcd_swizzle, int group) {
-  constexpr int TILE = 256 * 128; // 32 KiB per operand per buffer (K-128)
-  __shared__ unsigned char lds[2 * 2 * TILE + 2 * 2048];
-  unsigned char* const sbase = lds + 2 * 2 * TILE;
-
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
-  const long brow = (long)(wg / tiles_n) * 256;
-  const long bcol = (long)(wg % tiles_n) * 256;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid >> 1;
-  const int wc = wid & 1;
-  const int ks = K / 32;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
-  f32x16 acc[2][4] = {};
-
-  auto stage = [&](int buf, int k0) {
-    unsigned char* dst = lds + (long)buf * 2 * TILE;
-    for (int issue = 0; issue < 4; ++issue) {
-      long o_base = (long)issue * 8192 + (long)wid * 1024;
-      long o = o_base + (long)lane * 16;
-      int row = (int)(o >> 7);
-      int p = (int)((o & 127) >> 4);
-      int kk = ((p - (row >> 2)) & 7) * 16;
-      const unsigned char* ga = A + (brow + row) * (long)K + k0 + kk;
-      const unsigned char* gb = B + (bcol + row) * (long)K + k0 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(dst + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(dst + TILE + o_base), 16,
-          0, 0);
-    }
-    if (SCALED) {
-      const unsigned char* S = (wid < 4) ? As : Bs;
-      long rbase = (wid < 4) ? brow : bcol;
-      int srow = (wid & 3) * 64 + lane;
-      const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
-      unsigned char* sdst =
-          sbase + (long)buf * 2048 + (wid >= 4 ? 1024 : 0) + (wid & 3) * 256;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gs,
-          (__attribute__((address_space(3))) void*)sdst, 4, 0, 0);
-    }
-  };
-
-  const int g = lane >> 5;
-  const int r31 = lane & 31;
-  int a_off[2], asc_off[2], b_off[4], bsc_off[4];
-  for (int mf = 0; mf < 2; ++mf) {
-    int row = wr * 64 + mf * 32 + r31;
-    a_off[mf] = row * 128;
-    asc_off[mf] = row * 4 + g;
-  }
-  for (int nf = 0; nf < 4; ++nf) {
-    int col = wc * 128 + nf * 32 + r31;
-    b_off[nf] = col * 128;
-    bsc_off[nf] = col * 4 + g;
-  }
-  i32x8 afrag[2];
-  i32x8 bfrag[4];
-
-  stage(0, 0);
-  for (int k0 = 0; k0 < K; k0 += 128) {
-    const int cur = (k0 >> 7) & 1;
-    const bool more = (k0 + 128) < K;
-    if (more) stage(cur ^ 1, k0 + 128);
-    if (more)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(SCALED ? 9 : 8) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    const unsigned char* la = lds + (long)cur * 2 * TILE;
-    const unsigned char* lb = la + TILE;
-    const unsigned char* sA = sbase + (long)cur * 2048;
-    const unsigned char* sB = sA + 1024;
-    for (int kk = 0; kk < 2; ++kk) {
-      int asc[2];
-      for (int mf = 0; mf < 2; ++mf) {
-        int row = wr * 64 + mf * 32 + r31;
-        int rot = row >> 2;
-        int ch0 = (4 * kk + g + rot) & 7;      // half h=0
-        int ch1 = (4 * kk + 2 + g + rot) & 7;  // half h=1
-        *(i32x4*)&afrag[mf] = *(const i32x4*)__builtin_assume_aligned(
-            la + a_off[mf] + 16 * ch0, 16);
-        *((i32x4*)&afrag[mf] + 1) = *(const i32x4*)__builtin_assume_aligned(
-            la + a_off[mf] + 16 * ch1, 16);
-        asc[mf] = SCALED ? sA[asc_off[mf] + 2 * kk] : 127;
-      }
-      for (int nf = 0; nf < 4; ++nf) {
-        int col = wc * 128 + nf * 32 + r31;
-        int rot = col >> 2;
-        int ch0 = (4 * kk + g + rot) & 7;
-        int ch1 = (4 * kk + 2 + g + rot) & 7;
-        *(i32x4*)&bfrag[nf] = *(const i32x4*)__builtin_assume_aligned(
-            lb + b_off[nf] + 16 * ch0, 16);
-        *((i32x4*)&bfrag[nf] + 1) = *(const i32x4*)__builtin_assume_aligned(
-            lb + b_off[nf] + 16 * ch1, 16);
-        int bsc = SCALED ? sB[bsc_off[nf] + 2 * kk] : 127;
-        for (int mf = 0; mf < 2; ++mf)
-          acc[mf][nf] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-              afrag[mf], bfrag[nf], acc[mf][nf], 0, 0, 0, asc[mf], 0, bsc);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-
-  for (int mf = 0; mf < 2; ++mf)
-    for (int nf = 0; nf < 4; ++nf) {
-      long col = bcol + wc * 128 + nf * 32 + r31;
-      for (int r = 0; r < 16; ++r) {
-        long row = brow + wr * 64 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        C[row * (long)N + col] = acc[mf][nf][r];
-      }
-    }
-}
-
-void launch_gemm_mxfp8_nt(float* C, const void* A, const void* B,
-                          const void* As, const void* Bs, long M, long N,
-                          long K, hipStream_t stream, int xcd_swizzle) {
-  const GemmVariant var = gemm_variant_id("mxfp8", M, N, K);
-  const unsigned char* a = (const unsigned char*)A;
-  const unsigned char* b = (const unsigned char*)B;
-  const unsigned char* as = (const unsigned char*)As;
-  const unsigned char* bs = (const unsigned char*)Bs;
-  if (var == GemmVariant::mxfp8_32) {
-    int tn32 = (int)(N / 256);
-    int n32 = (int)(M / 256) * tn32;
-    hipLaunchKernelGGL((k_gemm_mxfp8_nt_32<true>), dim3(n32), dim3(512), 0,
-                       stream, C, a, b, as, bs, (int)M, (int)N, (int)K, tn32,
-                       n32, xcd_swizzle, gemm_group32());
-    check_hip(hipGetLastError(), "launch_gemm_mxfp8_nt(32)");
-    return;
-  }
-  const int grp = gemm_group((int)(N / 128));
-  int tiles_n = (int)(N / 128);
-  int nwg = (int)(M / 128) * tiles_n;
-  hipLaunchKernelGGL(k_gemm_mxfp8_nt, dim3(nwg), dim3(512), 0, stream, C, a,
-                     b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
-                     xcd_swizzle, grp);
-  check_hip(hipGetLastError(), "launch_gemm_mxfp8_nt");
-}
-
-
-
-// 4-wave variant: same diagonal-layout staging, 64x64 per wave (MREP =
-// NREP = 4) — 16 MFMAs per wave per K-tile instead of 8, halving the
-// relative cost of the per-tile barrier + staging-drain stall that PMC
-// shows dominating the 8-wave kernel (MfmaUtil 20.6%). HPK_MX4_WAVES
-// selects; the launcher defaults to the measured winner.
-__global__ __launch_bounds__(256) void k_gemm_mxfp4_nt_w4(
-    float* __restrict__ C, const unsigned char* __restrict__ A,
-    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
-    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
-    int nwg, int xcd_swizzle, int group) {
-  constexpr int MREP = 4, NREP = 4; // 4 waves as 2x2, 64x64 per wave
-  __shared__ unsigned char lds[2 * 128 * MX4B + 2 * 512];
-
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
-  const long brow = (long)(wg / tiles_n) * 128;
-  const long bcol = (long)(wg % tiles_n) * 128;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid >> 1;
-  const int wc = wid & 1;
-  const int ks = K / 32;
-  const long Kb = (long)K / 2;
-
-  unsigned char* sA = lds + 2 * 128 * MX4B;
-  unsigned char* sB = sA + 512;
-  f32x4 acc[MREP][NREP] = {};
-
-  for (int k0 = 0; k0 < K; k0 += 128) {
-    __syncthreads();
-    // data: [128][64] bytes per operand = 256 threads x 16 B x 2 issues
-    for (int issue = 0; issue < 2; ++issue) {
-      long o_base = (long)issue * 4096 + (long)wid * 1024;
-      long o = o_base + (long)lane * 16;
-      int row = (int)(o >> 6);
-      int kk = (int)(o & 63);
-      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
-      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(lds + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(lds + 128 * MX4B + o_base),
-          16, 0, 0);
-    }
-    // scales: 512 entries per operand, 2 per thread
-    {
-      int e0 = tid * 2;
-      int row = e0 >> 2, kb = e0 & 3;
-      sA[e0] = As[(brow + row) * (long)ks + k0 / 32 + kb];
-      sB[e0] = Bs[(bcol + row) * (long)ks + k0 / 32 + kb];
-      int e1 = e0 + 1;
-      int row1 = e1 >> 2, kb1 = e1 & 3;
-      sA[e1] = As[(brow + row1) * (long)ks + k0 / 32 + kb1];
-      sB[e1] = Bs[(bcol + row1) * (long)ks + k0 / 32 + kb1];
-    }
-    __syncthreads();
-
-    const int g = lane >> 4;
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
-    auto frag16 = [&](const unsigned char* base, long byteoff) {
-      i32x4 lo = *(const i32x4*)__builtin_assume_aligned(base + byteoff, 16);
-      i32x8 f = {};
-      for (int j = 0; j < 4; ++j) f[j] = lo[j];
-      return f;
-    };
-    i32x8 afrag[MREP];
-    int asc[MREP];
-    for (int m = 0; m < MREP; ++m) {
-      int row = wr * 64 + m * 16 + (lane & 15);
-      afrag[m] = frag16(lds, (long)row * MX4B + 16 * g);
-      asc[m] = sA[row * 4 + g];
-    }
-    for (int n = 0; n < NREP; ++n) {
-      int col = wc * 64 + n * 16 + (lane & 15);
-      i32x8 bfrag = frag16(lds + 128 * MX4B, (long)col * MX4B + 16 * g);
-      int bsc = sB[col * 4 + g];
-      for (int m = 0; m < MREP; ++m)
-        acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            afrag[m], bfrag, acc[m][n], 4, 4, 0, asc[m], 0, bsc);
-    }
-  }
-
-  for (int m = 0; m < MREP; ++m)
-    for (int n = 0; n < NREP; ++n) {
-      long row0 = brow + wr * 64 + m * 16 + 4 * (lane >> 4);
-      long col = bcol + wc * 64 + n * 16 + (lane & 15);
-      for (int r = 0; r < 4; ++r)
-        C[(row0 + r) * (long)N + col] = acc[m][n][r];
-    }
-}
-
-
-// Double-buffered variant: tile t+1's staging DMAs issue before tile t's
-// compute and a counted s_waitcnt retires exactly tile t's (the bf16 db
-// discipline, findings #18). ALL staging is global_load_lds — including
-// the scales, gathered as 4-byte dwords by waves 0-3 (K % 128 makes the
-// scale rows dword-aligned) — so the per-wave vmcnt count is exact
-// (3 issues for waves 0-3, 2 for waves 4-7; mixing ordinary loads into
-// the queue would break the count — the guide's load-kind trap). PMC
-// motivation: the plain kernel's MfmaUtil is 20.6% — each tile eats a
-// full memory latency inside the barrier window; with 34 KiB LDS and 85
-// VGPRs two 8-wave blocks stay resident on top of the intra-block
-// prefetch. HPK_MX4_WAVES=db selects... (launcher: HPK_GEMM_VARIANT
-// conventions kept: default is the measured winner).
-__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt_db(
-    float* __restrict__ C, const unsigned char* __restrict__ A,
-    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
-    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
-    int nwg, int xcd_swizzle, int group) {
-  constexpr int MREP = 4, NREP = 2;
-  constexpr int TILE = 128 * MX4B; // 8 KiB per operand per buffer
-  // ONE shared array (a second __shared__ object would force vmcnt(0)
-  // before every ds_read): [buf][A|B data] x2, then [buf][sA|sB] x2
-  __shared__ unsigned char lds[2 * 2 * TILE + 2 * 1024];
-  unsigned char* const sbase = lds + 2 * 2 * TILE;
-
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
-  const long brow = (long)(wg / tiles_n) * 128;
-  const long bcol = (long)(wg % tiles_n) * 128;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid >> 2;
-  const int wc = wid & 3;
-  const int ks = K / 32;
-  const long Kb = (long)K / 2;
-
-  f32x4 acc[MREP][NREP] = {};
-
-  auto stage = [&](int buf, int k0) {
-    unsigned char* dst = lds + (long)buf * 2 * TILE;
-    long o_base = (long)wid * 1024;
-    long o = o_base + (long)lane * 16;
-    int row = (int)(o >> 6);
-    int kk = (int)(o & 63);
-    const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
-    const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)ga,
-        (__attribute__((address_space(3))) void*)(dst + o_base), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gb,
-        (__attribute__((address_space(3))) void*)(dst + TILE + o_base), 16, 0,
-        0);
-    if (wid < 4) {
-      // scale dwords: wave w, lane l gathers rows (w&1)*64+l of As (w<2)
-      // or Bs — dest layout stays s[row*4 + kb]
-      const unsigned char* S = (wid < 2) ? As : Bs;
-      long rbase = (wid < 2) ? brow : bcol;
-      int srow = (wid & 1) * 64 + lane;
-      const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
-      unsigned char* sdst =
-          sbase + (long)buf * 1024 + (wid >= 2 ? 512 : 0) + (wid & 1) * 256;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gs,
-          (__attribute__((address_space(3))) void*)sdst, 4, 0, 0);
-    }
-  };
-
-  // VALU-diet (PMC showed 4 VALU per MFMA on the lambda version):
-  // per-lane LDS byte offsets are K-invariant — compute once; operand
-  // i32x8s persist across the loop so their top halves (unused in fp4
-  // mode) stay zero with no per-tile re-init/copies.
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
-  const int g = lane >> 4;
-  int a_off[MREP], asc_off[MREP], b_off[NREP], bsc_off[NREP];
-  for (int m = 0; m < MREP; ++m) {
-    int row = wr * 64 + m * 16 + (lane & 15);
-    a_off[m] = row * MX4B + 16 * g;
-    asc_off[m] = row * 4 + g;
-  }
-  for (int n = 0; n < NREP; ++n) {
-    int col = wc * 32 + n * 16 + (lane & 15);
-    b_off[n] = col * MX4B + 16 * g;
-    bsc_off[n] = col * 4 + g;
-  }
-  i32x8 afrag[MREP] = {};
-  i32x8 bfrag[NREP] = {};
-
-  stage(0, 0);
-  for (int k0 = 0; k0 < K; k0 += 128) {
-    const int cur = (k0 >> 7) & 1;
-    const bool more = (k0 + 128) < K;
-    if (more) stage(cur ^ 1, k0 + 128);
-    if (more) {
-      if (wid < 4)
-        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    const unsigned char* la = lds + (long)cur * 2 * TILE;
-    const unsigned char* lb = la + TILE;
-    const unsigned char* sA = sbase + (long)cur * 1024;
-    const unsigned char* sB = sA + 512;
-    int asc[MREP];
-    for (int m = 0; m < MREP; ++m) {
-      *(i32x4*)&afrag[m] = *(const i32x4*)__builtin_assume_aligned(
-          la + a_off[m], 16);
-      asc[m] = sA[asc_off[m]];
-    }
-    for (int n = 0; n < NREP; ++n) {
-      *(i32x4*)&bfrag[n] = *(const i32x4*)__builtin_assume_aligned(
-          lb + b_off[n], 16);
-      int bsc = sB[bsc_off[n]];
-      for (int m = 0; m < MREP; ++m)
-        acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            afrag[m], bfrag[n], acc[m][n], 4, 4, 0, asc[m], 0, bsc);
-    }
-    // all waves done reading buf[cur] before the next prefetch overwrites
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-
-  for (int m = 0; m < MREP; ++m)
-    for (int n = 0; n < NREP; ++n) {
-      long row0 = brow + wr * 64 + m * 16 + 4 * (lane >> 4);
-      long col = bcol + wc * 32 + n * 16 + (lane & 15);
-      for (int r = 0; r < 4; ++r)
-        C[(row0 + r) * (long)N + col] = acc[m][n][r];
-    }
-}
-
-
-// 32x32x64 variant at a 256^2 tile: the bigger scaled MFMA
-// (mfma_scale_f32_32x32x64_f8f6f4, 9099 TF ubench) plus the bigger tile
-// attack the two measured walls in order: an un-skewed 64-byte-stride
-// tile read 8-way bank conflicts (SQ_LDS_BANK_CONFLICT = 4x MFMA count,
-// fixed by the (row>>3)&3 chunk rotation below), and the 128^2 tile's
-// arithmetic intensity (254 FLOP/staged-byte = a ~2.0 PF HBM ceiling at
-// 8 TB/s — the measured 2.0-2.1 PF plateau of ALL 128^2 fp4 variants).
-// 256^2 doubles intensity (508 FLOP/B -> ~4 PF ceiling). fp4_probe3
-// measured the same DIAGONAL operand/scale layout at this shape: lane
-// (row=lane&31, g=lane>>5) supplies OCP block k in [32g,32g+32),
-// own-lane scale byte. 8 waves as 4x2 (64x128 per wave, 16 MFMAs per
-// K-128 tile), f32x16 accumulators (128 AGPRs), double-buffered
-// all-glds staging (scale rows as size-4 glds: sub-dword glds lands in
-// 4-byte-per-lane LDS slots — measured, and a K-128 tile's 4 scale
-// bytes fill the slot exactly).
-__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt_32(
-    float* __restrict__ C, const unsigned char* __restrict__ A,
-    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
-    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
-    int nwg, int xcd_swizzle, int group) {
-  constexpr int TILE = 256 * 64; // 16 KiB per operand per buffer (K-128)
-  __shared__ unsigned char lds[2 * 2 * TILE + 2 * 2048];
-  unsigned char* const sbase = lds + 2 * 2 * TILE;
-
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
-  const long brow = (long)(wg / tiles_n) * 256;
-  const long bcol = (long)(wg % tiles_n) * 256;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid >> 1; // 4 wave-rows of 64
-  const int wc = wid & 1;  // 2 wave-cols of 128
-  const int ks = K / 32;
-  const long Kb = (long)K / 2;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
-  f32x16 acc[2][4] = {};
-
-  auto stage = [&](int buf, int k0) {
-    unsigned char* dst = lds + (long)buf * 2 * TILE;
-    // anti-bank-conflict chunk rotation: LDS chunk position p of row r
-    // holds global chunk (p - (r>>3)) & 3 (true-lane-group enumeration
-    // in tests/test_gemm_skew_logic.py); glds keeps LDS lane-linear so
-    // the rotation is applied to the SOURCE chunk address
-    for (int issue = 0; issue < 2; ++issue) {
-      long o_base = (long)issue * 8192 + (long)wid * 1024;
-      long o = o_base + (long)lane * 16;
-      int row = (int)(o >> 6);
-      int p = (int)((o & 63) >> 4);
-      int kk = ((p - (row >> 3)) & 3) * 16;
-      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
-      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(dst + o_base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(dst + TILE + o_base), 16,
-          0, 0);
-    }
-    // scales: one dword per row (K-128 tile = 4 e8m0 bytes); waves 0-3
-    // gather As rows wid*64+lane, waves 4-7 Bs
-    const unsigned char* S = (wid < 4) ? As : Bs;
-    long rbase = (wid < 4) ? brow : bcol;
-    int srow = (wid & 3) * 64 + lane;
-    const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
-    unsigned char* sdst =
-        sbase + (long)buf * 2048 + (wid >= 4 ? 1024 : 0) + (wid & 3) * 256;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gs,
-        (__attribute__((address_space(3))) void*)sdst, 4, 0, 0);
-  };
-
-  // K-invariant per-lane offsets
-  const int g = lane >> 5;
-  const int r31 = lane & 31;
-  int a_off[2], asc_off[2], b_off[4], bsc_off[4];
-  for (int mf = 0; mf < 2; ++mf) {
-    int row = wr * 64 + mf * 32 + r31;
-    a_off[mf] = row * 64;
-    asc_off[mf] = row * 4 + g;
-  }
-  for (int nf = 0; nf < 4; ++nf) {
-    int col = wc * 128 + nf * 32 + r31;
-    b_off[nf] = col * 64;
-    bsc_off[nf] = col * 4 + g;
-  }
-  i32x8 afrag[2] = {};
-  i32x8 bfrag[4] = {};
-
-  stage(0, 0);
-  for (int k0 = 0; k0 < K; k0 += 128) {
-    const int cur = (k0 >> 7) & 1;
-    const bool more = (k0 + 128) < K;
-    if (more) stage(cur ^ 1, k0 + 128);
-    if (more)
-      asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    const unsigned char* la = lds + (long)cur * 2 * TILE;
-    const unsigned char* lb = la + TILE;
-    const unsigned char* sA = sbase + (long)cur * 2048;
-    const unsigned char* sB = sA + 1024;
-    for (int kk = 0; kk < 2; ++kk) {
-      int asc[2];
-      for (int mf = 0; mf < 2; ++mf) {
-        int row = wr * 64 + mf * 32 + r31;
-        int ch = (g + 2 * kk + (row >> 3)) & 3;
-        *(i32x4*)&afrag[mf] = *(const i32x4*)__builtin_assume_aligned(
-            la + a_off[mf] + 16 * ch, 16);
-        asc[mf] = sA[asc_off[mf] + 2 * kk];
-      }
-      for (int nf = 0; nf < 4; ++nf) {
-        int col = wc * 128 + nf * 32 + r31;
-        int ch = (g + 2 * kk + (col >> 3)) & 3;
-        *(i32x4*)&bfrag[nf] = *(const i32x4*)__builtin_assume_aligned(
-            lb + b_off[nf] + 16 * ch, 16);
-        int bsc = sB[bsc_off[nf] + 2 * kk];
-        for (int mf = 0; mf < 2; ++mf)
-          acc[mf][nf] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-              afrag[mf], bfrag[nf], acc[mf][nf], 4, 4, 0, asc[mf], 0, bsc);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-
-  for (int mf = 0; mf < 2; ++mf)
-    for (int nf = 0; nf < 4; ++nf) {
-      long col = bcol + wc * 128 + nf * 32 + r31;
-      for (int r = 0; r < 16; ++r) {
-        long row = brow + wr * 64 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        C[row * (long)N + col] = acc[mf][nf][r];
-      }
-    }
-}
-
-
-// 256x128-tile variant of the 32x32x64 mx4 kernel: the occupancy
-// experiment the final PMC motivates (181 VGPR x 2 waves/SIMD = one
-// resident block; nothing covers the barrier windows, MfmaUtil 35%).
-// Halving the N-tile drops the accumulator floor to 64 VGPRs/lane so
-// TWO 8-wave blocks co-reside (4 waves/SIMD) and cover each other's
-// waits — at the price of arithmetic intensity (341 vs 508
-// FLOP/staged-byte). 8 waves as 4x2 of 64x64; per-wave glds counts
-// differ (A 2 issues + B 1 for all waves, + 1 scale issue for waves
-// 0-5), so the counted vmcnt branches per wave.
-__global__ __launch_bounds__(512) void k_gemm_mxfp4_nt_32h(
-    float* __restrict__ C, const unsigned char* __restrict__ A,
-    const unsigned char* __restrict__ B, const unsigned char* __restrict__ As,
-    const unsigned char* __restrict__ Bs, int M, int N, int K, int tiles_n,
-    int nwg, int xcd_swizzle, int group) {
-  constexpr int ATILE = 256 * 64; // 16 KiB
-  constexpr int BTILE = 128 * 64; // 8 KiB
-  __shared__ unsigned char lds[2 * (ATILE + BTILE) + 2 * 1536];
-  unsigned char* const sbase = lds + 2 * (ATILE + BTILE);
-
-  int wg = (int)blockIdx.x;
-  if (xcd_swizzle) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = wg % 8, i = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  wg = hpk_group_remap(wg, tiles_n, nwg, group);
-  const long brow = (long)(wg / tiles_n) * 256;
-  const long bcol = (long)(wg % tiles_n) * 128;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid >> 1; // 4 wave-rows of 64
-  const int wc = wid & 1;  // 2 wave-cols of 64
-  const int ks = K / 32;
-  const long Kb = (long)K / 2;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
-  f32x16 acc[2][2] = {};
-
-  auto stage = [&](int buf, int k0) {
-    unsigned char* dst = lds + (long)buf * (ATILE + BTILE);
-    for (int issue = 0; issue < 2; ++issue) { // A: 256 rows
-      long o_base = (long)issue * 8192 + (long)wid * 1024;
-      long o = o_base + (long)lane * 16;
-      int row = (int)(o >> 6);
-      int p = (int)((o & 63) >> 4);
-      int kk = ((p - (row >> 3)) & 3) * 16;
-      const unsigned char* ga = A + (brow + row) * Kb + k0 / 2 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)(dst + o_base), 16, 0, 0);
-    }
-    { // B: 128 rows, one issue
-      long o_base = (long)wid * 1024;
-      long o = o_base + (long)lane * 16;
-      int row = (int)(o >> 6);
-      int p = (int)((o & 63) >> 4);
-      int kk = ((p - (row >> 3)) & 3) * 16;
-      const unsigned char* gb = B + (bcol + row) * Kb + k0 / 2 + kk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gb,
-          (__attribute__((address_space(3))) void*)(dst + ATILE + o_base), 16,
-          0, 0);
-    }
-    if (wid < 6) { // scales: A rows 0-255 (waves 0-3), B rows 0-127 (4-5)
-      const unsigned char* S = (wid < 4) ? As : Bs;
-      long rbase = (wid < 4) ? brow : bcol;
-      int srow = (wid < 4 ? (wid & 3) : (wid & 1)) * 64 + lane;
-      const unsigned char* gs = S + (rbase + srow) * (long)ks + k0 / 32;
-      unsigned char* sdst = sbase + (long)buf * 1536 +
-                            (wid < 4 ? (wid & 3) * 256 : 1024 + (wid & 1) * 256);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gs,
-          (__attribute__((address_space(3))) void*)sdst, 4, 0, 0);
-    }
-  };
-
-  const int g = lane >> 5;
-  const int r31 = lane & 31;
-  int a_off[2], asc_off[2], b_off[2], bsc_off[2];
-  for (int mf = 0; mf < 2; ++mf) {
-    int row = wr * 64 + mf * 32 + r31;
-    a_off[mf] = row * 64;
-    asc_off[mf] = row * 4 + g;
-  }
-  for (int nf = 0; nf < 2; ++nf) {
-    int col = wc * 64 + nf * 32 + r31;
-    b_off[nf] = col * 64;
-    bsc_off[nf] = col * 4 + g;
-  }
-  i32x8 afrag[2] = {};
-  i32x8 bfrag[2] = {};
-
-  stage(0, 0);
-  for (int k0 = 0; k0 < K; k0 += 128) {
-    const int cur = (k0 >> 7) & 1;
-    const bool more = (k0 + 128) < K;
-    if (more) stage(cur ^ 1, k0 + 128);
-    if (more) {
-      if (wid < 6)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    const unsigned char* la = lds + (long)cur * (ATILE + BTILE);
-    const unsigned char* lb = la + ATILE;
-    const unsigned char* sA = sbase + (long)cur * 1536;
-    const unsigned char* sB = sA + 1024;
-    for (int kk = 0; kk < 2; ++kk) {
-      int asc[2];
-      for (int mf = 0; mf < 2; ++mf) {
-        int row = wr * 64 + mf * 32 + r31;
-        int ch = (g + 2 * kk + (row >> 3)) & 3;
-        *(i32x4*)&afrag[mf] = *(const i32x4*)__builtin_assume_aligned(
-            la + a_off[mf] + 16 * ch, 16);
-        asc[mf] = sA[asc_off[mf] + 2 * kk];
-      }
-      for (int nf = 0; nf < 2; ++nf) {
-        int col = wc * 64 + nf * 32 + r31;
-        int ch = (g + 2 * kk + (col >> 3)) & 3;
-        *(i32x4*)&bfrag[nf] = *(const i32x4*)__builtin_assume_aligned(
-            lb + b_off[nf] + 16 * ch, 16);
-        int bsc = sB[bsc_off[nf] + 2 * kk];
-        for (int mf = 0; mf < 2; ++mf)
-          acc[mf][nf] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-              afrag[mf], bfrag[nf], acc[mf][nf], 4, 4, 0, asc[mf], 0, bsc);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-
-  for (int mf = 0; mf < 2; ++mf)
-    for (int nf = 0; nf < 2; ++nf) {
-      long col = bcol + wc * 64 + nf * 32 + r31;
-      for (int r = 0; r < 16; ++r) {
-        long row = brow + wr * 64 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        C[row * (long)N + col] = acc[mf][nf][r];
-      }
-    }
-}
-
-void launch_gemm_mxfp4_nt(float* C, const void* A, const void* B,
-                          const void* As, const void* Bs, long M, long N,
-                          long K, hipStream_t stream, int xcd_swizzle) {
-  const GemmVariant var = gemm_variant_id("mxfp4", M, N, K);
-  const unsigned char* a = (const unsigned char*)A;
-  const unsigned char* b = (const unsigned char*)B;
-  const unsigned char* as = (const unsigned char*)As;
-  const unsigned char* bs = (const unsigned char*)Bs;
-  const int grp = gemm_group((int)(N / 128));
-  int tiles_n = (int)(N / 128);
-  int nwg = (int)(M / 128) * tiles_n;
-  switch (var) {
-  case GemmVariant::mxfp4_32: {
-    int tn32 = (int)(N / 256);
-    int n32 = (int)(M / 256) * tn32;
-    hipLaunchKernelGGL(k_gemm_mxfp4_nt_32, dim3(n32), dim3(512), 0, stream,
-                       C, a, b, as, bs, (int)M, (int)N, (int)K, tn32, n32,
-                       xcd_swizzle, gemm_group32());
-    break;
-  }
-  case GemmVariant::mxfp4_32h: {
-    int tnh = (int)(N / 128);
-    int nh = (int)(M / 256) * tnh;
-    hipLaunchKernelGGL(k_gemm_mxfp4_nt_32h, dim3(nh), dim3(512), 0, stream,
-                       C, a, b, as, bs, (int)M, (int)N, (int)K, tnh, nh,
-                       xcd_swizzle, gemm_group32());
-    break;
-  }
-  case GemmVariant::mxfp4_db:
-    hipLaunchKernelGGL(k_gemm_mxfp4_nt_db, dim3(nwg), dim3(512), 0, stream,
-                       C, a, b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
-    break;
-  case GemmVariant::mxfp4_w4:
-    hipLaunchKernelGGL(k_gemm_mxfp4_nt_w4, dim3(nwg), dim3(256), 0, stream,
-                       C, a, b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
-    break;
+  const char* what = "launch_gemm_bf16_nt";
+  switch (gemm_variant_id("bf16", M, N, K)) {
+  case GemmVariant::bf16_8ph:
+    return launch_tiled(k_gemm_bf16_8ph, "launch_gemm_bf16_nt(8ph)", 256, 256,
+                        512, grp, g, C, a, b);
+  case GemmVariant::bf16_db8:
+    return launch_tiled(k_gemm_bf16_nt_db<2, 4>, what, BM, BN, 512, grp, g, C,
+                        a, b);
+  case GemmVariant::bf16_db4:
+    return launch_tiled(k_gemm_bf16_nt_db<2, 2>, what, BM, BN, 256, grp, g, C,
+                        a, b);
+  case GemmVariant::bf16_plain8:
+    return launch_tiled(k_gemm_bf16_nt<2, 4>, what, BM, BN, 512, grp, g, C, a,
+                        b);
   default:
-    hipLaunchKernelGGL(k_gemm_mxfp4_nt, dim3(nwg), dim3(512), 0, stream, C,
-                       a, b, as, bs, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
+    return launch_tiled(k_gemm_bf16_nt<2, 2>, what, BM, BN, 256, grp, g, C, a,
+                        b);
   }
-  check_hip(hipGetLastError(), "launch_gemm_mxfp4_nt");
 }
 
 void launch_gemm_fp8_nt(float* C, const void* A, const void* B, long M,
                         long N, long K, hipStream_t stream,
                         int xcd_swizzle) {
-  const GemmVariant var = gemm_variant_id("fp8", M, N, K);
+  const GemmCall g{M, N, K, stream, xcd_swizzle};
   const unsigned char* a = (const unsigned char*)A;
   const unsigned char* b = (const unsigned char*)B;
+  const unsigned char* none = nullptr; // SCALED=false reads no scales
   const int grp = gemm_group((int)(N / 256));
-  switch (var) {
-  case GemmVariant::fp8_32: {
-    int tn32 = (int)(N / 256);
-    int n32 = (int)(M / 256) * tn32;
-    hipLaunchKernelGGL((k_gemm_mxfp8_nt_32<false>), dim3(n32), dim3(512), 0,
-                       stream, C, a, b, nullptr, nullptr, (int)M, (int)N,
-                       (int)K, tn32, n32, xcd_swizzle, gemm_group32());
-    check_hip(hipGetLastError(), "launch_gemm_fp8_nt(32)");
-    return;
-  }
-  case GemmVariant::fp8_8ph: {
-    int tn = (int)(N / 256);
-    int n8 = (int)(M / 256) * tn;
-    hipLaunchKernelGGL(k_gemm_fp8_8ph, dim3(n8), dim3(512), 0, stream, C, a,
-                       b, (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
-    check_hip(hipGetLastError(), "launch_gemm_fp8_nt(8ph)");
-    return;
-  }
-  default: {
-    int tiles_n = (int)(N / BN);
-    int nwg = (int)(M / BM) * tiles_n;
-    hipLaunchKernelGGL((k_gemm_fp8_nt<2, 4>), dim3(nwg), dim3(512), 0, stream,
-                       C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
-    check_hip(hipGetLastError(), "launch_gemm_fp8_nt");
-  }
+  switch (gemm_variant_id("fp8", M, N, K)) {
+  case GemmVariant::fp8_32:
+    return launch_tiled(k_gemm_mxfp8_nt_32<false>, "launch_gemm_fp8_nt(32)",
+                        256, 256, 512, gemm_group32(), g, C, a, b, none, none);
+  case GemmVariant::fp8_8ph:
+    return launch_tiled(k_gemm_fp8_8ph, "launch_gemm_fp8_nt(8ph)", 256, 256,
+                        512, grp, g, C, a, b);
+  default:
+    return launch_tiled(k_gemm_fp8_nt<2, 4>, "launch_gemm_fp8_nt", BM, BN,
+                        512, grp, g, C, a, b);
   }
 }
 
-void launch_gemm_bf16_nt(float* C, const void* A, const void* B, long M,
-                         long N, long K, hipStream_t stream,
-                         int xcd_swizzle) {
-  const GemmVariant var = gemm_variant_id("bf16", M, N, K);
-  const __hip_bfloat16* a = (const __hip_bfloat16*)A;
-  const __hip_bfloat16* b = (const __hip_bfloat16*)B;
+void launch_gemm_i8_nt(int* C, const void* A, const void* B, long M,
+                       long N, long K, hipStream_t stream, int xcd_swizzle) {
+  const GemmCall g{M, N, K, stream, xcd_swizzle};
+  const signed char* a = (const signed char*)A;
+  const signed char* b = (const signed char*)B;
   const int grp = gemm_group((int)(N / 256));
-  int tiles_n = (int)(N / BN);
-  int nwg = (int)(M / BM) * tiles_n;
-  switch (var) {
-  case GemmVariant::bf16_8ph: {
-    int tn = (int)(N / 256);
-    int n8 = (int)(M / 256) * tn;
-    hipLaunchKernelGGL(k_gemm_bf16_8ph, dim3(n8), dim3(512), 0, stream, C, a,
-                       b, (int)M, (int)N, (int)K, tn, n8, xcd_swizzle, grp);
-    check_hip(hipGetLastError(), "launch_gemm_bf16_nt(8ph)");
-    return;
-  }
-  case GemmVariant::bf16_db8:
-    hipLaunchKernelGGL((k_gemm_bf16_nt_db<2, 4>), dim3(nwg), dim3(512), 0,
-                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
-    break;
-  case GemmVariant::bf16_db4:
-    hipLaunchKernelGGL((k_gemm_bf16_nt_db<2, 2>), dim3(nwg), dim3(256), 0,
-                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
-    break;
-  case GemmVariant::bf16_plain8:
-    hipLaunchKernelGGL((k_gemm_bf16_nt<2, 4>), dim3(nwg), dim3(512), 0,
-                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
-    break;
+  switch (gemm_variant_id("i8", M, N, K)) {
+  case GemmVariant::i8_32:
+    return launch_tiled(k_gemm_i8_nt_32, "launch_gemm_i8_nt(32)", 256, 256,
+                        512, gemm_group32(), g, C, a, b);
+  case GemmVariant::i8_8ph:
+    return launch_tiled(k_gemm_i8_8ph, "launch_gemm_i8_nt(8ph)", 256, 256,
+                        512, grp, g, C, a, b);
   default:
-    hipLaunchKernelGGL((k_gemm_bf16_nt<2, 2>), dim3(nwg), dim3(256), 0,
-                       stream, C, a, b, (int)M, (int)N, (int)K, tiles_n, nwg,
-                       xcd_swizzle, grp);
+    return launch_tiled(k_gemm_i8_nt<2, 4>, "launch_gemm_i8_nt", BM, BN, 512,
+                        grp, g, C, a, b);
   }
-  check_hip(hipGetLastError(), "launch_gemm_bf16_nt");
+}
+
+void launch_gemm_mxfp8_nt(float* C, const void* A, const void* B,
+                          const void* As, const void* Bs, long M, long N,
+                          long K, hipStream_t stream, int xcd_swizzle) {
+  const GemmCall g{M, N, K, stream, xcd_swizzle};
+  const unsigned char* a = (const unsigned char*)A;
+  const unsigned char* b = (const unsigned char*)B;
+  const unsigned char* as = (const unsigned char*)As;
+  const unsigned char* bs = (const unsigned char*)Bs;
+  switch (gemm_variant_id("mxfp8", M, N, K)) {
+  case GemmVariant::mxfp8_32:
+    return launch_tiled(k_gemm_mxfp8_nt_32<true>, "launch_gemm_mxfp8_nt(32)",
+                        256, 256, 512, gemm_group32(), g, C, a, b, as, bs);
+  default:
+    return launch_tiled(k_gemm_mxfp8_nt, "launch_gemm_mxfp8_nt", 128, 128,
+                        512, gemm_group((int)(N / 128)), g, C, a, b, as, bs);
+  }
+}
+
+void launch_gemm_mxfp4_nt(float* C, const void* A, const void* B,
+                          const void* As, const void* Bs, long M, long N,
+                          long K, hipStream_t stream, int xcd_swizzle) {
+  const GemmCall g{M, N, K, stream, xcd_swizzle};
+  const unsigned char* a = (const unsigned char*)A;
+  const unsigned char* b = (const unsigned char*)B;
+  const unsigned char* as = (const unsigned char*)As;
+  const unsigned char* bs = (const unsigned char*)Bs;
+  const int grp = gemm_group((int)(N / 128));
+  const char* what = "launch_gemm_mxfp4_nt";
+  switch (gemm_variant_id("mxfp4", M, N, K)) {
+  case GemmVariant::mxfp4_32:
+    return launch_tiled(k_gemm_mxfp4_nt_32, what, 256, 256, 512,
+                        gemm_group32(), g, C, a, b, as, bs);
+  case GemmVariant::mxfp4_32h:
+    return launch_tiled(k_gemm_mxfp4_nt_32h, what, 256, 128, 512,
+                        gemm_group32(), g, C, a, b, as, bs);
+  case GemmVariant::mxfp4_db:
+    return launch_tiled(k_gemm_mxfp4_nt_db, what, 128, 128, 512, grp, g, C, a,
+                        b, as, bs);
+  case GemmVariant::mxfp4_w4:
+    return launch_tiled(k_gemm_mxfp4_nt_w4, what, 128, 128, 256, grp, g, C,
+                        a, b, as, bs);
+  default:
+    return launch_tiled(k_gemm_mxfp4_nt, what, 128, 128, 512, grp, g, C,
+                        a, b, as, bs);
+  }
 }
 
 } // namespace hpk
