@@ -59,7 +59,9 @@ $(BUILD)/ext.o: $(NATIVE)/ext.cpp $(NATIVE)/include/hpk.h | $(BUILD)
 $(EXT_SO): $(BUILD)/ext.o $(LIB_OBJS)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) -shared $^ -o $@ $(LDFLAGS)
 
-$(BUILD)/%_main.o: cpp/%_main.cpp $(NATIVE)/include/hpk.h | $(BUILD)
+MAIN_HDRS  := $(NATIVE)/include/hpk.h cpp/miniapp_util.h cpp/launch_util.h
+
+$(BUILD)/%_main.o: cpp/%_main.cpp $(MAIN_HDRS) | $(BUILD)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 $(BIN)/hpk_conc: $(BUILD)/conc_main.o $(LIB_OBJS) | $(BIN)
@@ -83,7 +85,7 @@ $(BIN)/hpk_membench: $(BUILD)/membench_main.o $(LIB_OBJS) | $(BIN)
 # dedicated rule (NOT a target-specific CXXFLAGS append: `make asan`
 # overrides CXXFLAGS on the command line, which would drop the append) —
 # the shorter-stem pattern beats the generic %_main.o rule
-$(BUILD)/mpi_%_main.o: cpp/mpi_%_main.cpp $(NATIVE)/include/hpk.h | $(BUILD)
+$(BUILD)/mpi_%_main.o: cpp/mpi_%_main.cpp $(MAIN_HDRS) $(NATIVE)/include/mpi_datatype.h | $(BUILD)
 	$(HIPCC) $(CXXFLAGS) $(MPI_CFLAGS) -c $< -o $@
 
 $(BIN)/hpk_mpi_allreduce: $(BUILD)/mpi_allreduce_main.o $(LIB_OBJS) | $(BIN)

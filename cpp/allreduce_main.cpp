@@ -38,6 +38,7 @@
 #include "../hpc_patterns_amd/native/include/hpk.h"
 #include "../hpc_patterns_amd/native/include/rccl_datatype.h"
 #include "launch_util.h"
+#include "miniapp_util.h"
 
 #include <rccl/rccl.h>
 #include <sys/mman.h>
@@ -45,7 +46,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -55,19 +55,9 @@
 
 namespace {
 
-void check_nccl(ncclResult_t r, const char* what) {
-  if (r != ncclSuccess) {
-    std::fprintf(stderr, "RCCL error in %s: %s\n", what,
-                 ncclGetErrorString(r));
-    std::exit(1);
-  }
-}
-
-double now_s() {
-  return std::chrono::duration<double>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
+using hpk_app::alloc_buf;
+using hpk_app::now_s;
+using hpk_launch::check_nccl;
 
 struct Config {
   int p = 25;
@@ -79,48 +69,6 @@ struct Config {
   int iters = 10;
   int chunks = 8;
 };
-
-// dtype dispatch for the device kernels (fill / accumulate / exact sum)
-template <typename T> struct Kern;
-template <> struct Kern<float> {
-  static void fill(float* p, float v, size_t n, hipStream_t s) {
-    hpk::launch_fill_f32(p, v, n, s);
-  }
-  static void acc(float* d, const float* s_, size_t n, hipStream_t s) {
-    hpk::launch_acc_f32(d, s_, n, s);
-  }
-  static double sum(const float* p, size_t n, hipStream_t s) {
-    return hpk::reduce_sum_f32(p, n, s);
-  }
-};
-template <> struct Kern<int> {
-  static void fill(int* p, int v, size_t n, hipStream_t s) {
-    hpk::launch_fill_i32(p, v, n, s);
-  }
-  static void acc(int* d, const int* s_, size_t n, hipStream_t s) {
-    hpk::launch_acc_i32(d, s_, n, s);
-  }
-  static double sum(const int* p, size_t n, hipStream_t s) {
-    return (double)hpk::reduce_sum_i32(p, n, s);
-  }
-};
-
-void* alloc_buf(char kind, size_t bytes) {
-  void* p = nullptr;
-  switch (kind) {
-    case 'D': hpk::check_hip(hipMalloc(&p, bytes), "hipMalloc"); break;
-    case 'H':
-      hpk::check_hip(hipHostMalloc(&p, bytes, hipHostMallocDefault),
-                     "hipHostMalloc");
-      break;
-    case 'S':
-      hpk::check_hip(hipMallocManaged(&p, bytes, hipMemAttachGlobal),
-                     "hipMallocManaged");
-      break;
-    default: std::abort();
-  }
-  return p;
-}
 
 // Ring exchange transports. The ring ALGORITHM below is transport-agnostic;
 // these provide one step's neighbour exchange:
@@ -219,10 +167,10 @@ double run_ring(Ring& ring, hipStream_t stream, T* va, T* vb,
                 T* vc, size_t n, int size, int* steps_out = nullptr) {
   double t0 = now_s();
   int steps = 0;
-  Kern<T>::acc(vc, va, n, stream); // VC += own VA (VC starts at 0)
+  hpk::launch_acc(vc, va, n, stream); // VC += own VA (VC starts at 0)
   for (int step = 0; step < size - 1; ++step) {
     ring.sendrecv(va, vb, n, stream);
-    Kern<T>::acc(vc, vb, n, stream);
+    hpk::launch_acc(vc, vb, n, stream);
     std::swap(va, vb);
     ++steps;
   }
@@ -247,7 +195,7 @@ double run_pipeline(ncclComm_t comm, hipStream_t comm_stream,
     hpk::check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "ev");
 
   double t0 = now_s();
-  Kern<T>::acc(vc, va, n, comp_stream);
+  hpk::launch_acc(vc, va, n, comp_stream);
   for (int step = 0; step < size - 1; ++step) {
     // launch all chunk exchanges; accumulate each chunk as soon as it lands
     for (int c = 0; c < chunks; ++c) {
@@ -262,7 +210,7 @@ double run_pipeline(ncclComm_t comm, hipStream_t comm_stream,
       check_nccl(ncclGroupEnd(), "group end");
       hpk::check_hip(hipEventRecord(done[c], comm_stream), "record");
       hpk::check_hip(hipStreamWaitEvent(comp_stream, done[c], 0), "wait");
-      Kern<T>::acc(vc + off, vb + off, len, comp_stream);
+      hpk::launch_acc(vc + off, vb + off, len, comp_stream);
     }
     // comm of next step must not overwrite vb before accumulate read it:
     // swap uses distinct buffers, but step s+1 recv into (old) va after
@@ -316,9 +264,9 @@ int worker(int rank, int size, int ndev, hpk_launch::SharedBootstrap* sh,
   int ring_steps = 0;
   for (int it = 0; it < cfg.iters; ++it) {
     // (re)initialize: VA = rank, VB = -1, VC = 0 (reference Initialize)
-    Kern<T>::fill(va, (T)rank, n, stream);
-    Kern<T>::fill(vb, (T)-1, n, stream);
-    Kern<T>::fill(vc, (T)0, n, stream);
+    hpk::launch_fill(va, (T)rank, n, stream);
+    hpk::launch_fill(vb, (T)-1, n, stream);
+    hpk::launch_fill(vc, (T)0, n, stream);
     hpk::check_hip(hipStreamSynchronize(stream), "init sync");
     // ipc transport: nobody may put into my freshly-filled recv buffer
     // before the fill above completed everywhere
@@ -363,18 +311,11 @@ int worker(int rank, int size, int ndev, hpk_launch::SharedBootstrap* sh,
     (void)hipFree(d_time);
   }
 
-  // analytic verification: every element == size*(size-1)/2
-  double expected = (double)n * ((double)size * (size - 1) / 2.0);
-  double got = Kern<T>::sum(vc, n, stream);
-  bool pass = std::abs(got - expected) < 1e-6 * std::max(1.0, expected);
-  std::printf("%s rank %d (sum %.1f, expected %.1f)\n",
-              pass ? "Passed" : "FAILED", rank, got, expected);
+  bool pass = hpk_app::allreduce_verdict(hpk::reduce_sum(vc, n, stream), n,
+                                         size, rank);
 
   if (rank == 0) {
-    double gb = (double)bytes / 1e9;
-    // bus bandwidth convention: ring moves 2(size-1)/size * bytes per rank
-    double busbw =
-        size > 1 ? 2.0 * (size - 1) / size * gb / max_time : gb / max_time;
+    double busbw = hpk_app::allreduce_busbw(bytes, size, max_time);
     std::printf("# algo=%s transport=%s dtype=%s ranks=%d elems=2^%d alloc=%c "
                 "steps=%d time=%.6fs busbw=%.2f GB/s\n",
                 cfg.algo.c_str(), cfg.transport.c_str(), cfg.dtype.c_str(),
@@ -393,10 +334,7 @@ int main(int argc, char* argv[]) {
   Config cfg;
   for (int i = 1; i < argc; ++i) {
     std::string s = argv[i];
-    auto next = [&]() -> const char* {
-      if (++i >= argc) { std::fprintf(stderr, "missing value\n"); std::exit(1); }
-      return argv[i];
-    };
+    auto next = [&] { return hpk_app::next_arg(i, argc, argv); };
     if (s == "--probe-ndev") {  // launch_util.h re-exec probe
       std::printf("%d\n", hpk::device_count());
       return 0;

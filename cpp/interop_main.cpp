@@ -18,6 +18,7 @@
 //     HIP accumulate kernel and re-verified.
 
 #include "../hpc_patterns_amd/native/include/hpk.h"
+#include "launch_util.h"
 
 #include <rccl/rccl.h>
 
@@ -25,12 +26,7 @@
 #include <cstdlib>
 #include <vector>
 
-static void check_nccl(ncclResult_t r, const char* what) {
-  if (r != ncclSuccess) {
-    std::fprintf(stderr, "RCCL error in %s: %s\n", what, ncclGetErrorString(r));
-    std::exit(1);
-  }
-}
+using hpk_launch::check_nccl;
 
 int main() {
   const size_t N = 1 << 20;

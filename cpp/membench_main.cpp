@@ -8,8 +8,8 @@
 //   hpk_membench [--quick] [--floats N]
 
 #include "../hpc_patterns_amd/native/include/hpk.h"
+#include "miniapp_util.h"
 
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -17,11 +17,7 @@
 
 namespace {
 
-double now_s() {
-  return std::chrono::duration<double>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
+using hpk_app::now_s;
 
 double time_best(const std::function<void()>& fn, int reps = 5, int warm = 2) {
   for (int i = 0; i < warm; ++i) fn();

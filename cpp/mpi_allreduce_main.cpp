@@ -31,11 +31,11 @@
 
 #include "../hpc_patterns_amd/native/include/hpk.h"
 #include "../hpc_patterns_amd/native/include/mpi_datatype.h"
+#include "miniapp_util.h"
 
 #include <mpi.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,18 +44,10 @@
 
 namespace {
 
-double now_s() {
-  return std::chrono::duration<double>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
-void check_mpi(int rc, const char* what) {
-  if (rc != MPI_SUCCESS) {
-    std::fprintf(stderr, "MPI error in %s: %d\n", what, rc);
-    MPI_Abort(MPI_COMM_WORLD, 1);
-  }
-}
+using hpk::check_mpi;
+using hpk_app::alloc_buf;
+using hpk_app::free_buf;
+using hpk_app::now_s;
 
 struct Config {
   int p = 25;
@@ -78,34 +70,6 @@ template <typename T> struct HostOps {
     double acc = 0.0;
     for (size_t i = 0; i < n; ++i) acc += (double)p[i];
     return acc;
-  }
-};
-
-template <typename T> struct DevOps;
-template <> struct DevOps<float> {
-  static void fill(float* p, float v, size_t n) {
-    hpk::launch_fill_f32(p, v, n, nullptr);
-    hpk::check_hip(hipStreamSynchronize(nullptr), "fill sync");
-  }
-  static void acc(float* d, const float* s, size_t n) {
-    hpk::launch_acc_f32(d, s, n, nullptr);
-    hpk::check_hip(hipStreamSynchronize(nullptr), "acc sync");
-  }
-  static double sum(const float* p, size_t n) {
-    return hpk::reduce_sum_f32(p, n, nullptr);
-  }
-};
-template <> struct DevOps<int> {
-  static void fill(int* p, int v, size_t n) {
-    hpk::launch_fill_i32(p, v, n, nullptr);
-    hpk::check_hip(hipStreamSynchronize(nullptr), "fill sync");
-  }
-  static void acc(int* d, const int* s, size_t n) {
-    hpk::launch_acc_i32(d, s, n, nullptr);
-    hpk::check_hip(hipStreamSynchronize(nullptr), "acc sync");
-  }
-  static double sum(const int* p, size_t n) {
-    return (double)hpk::reduce_sum_i32(p, n, nullptr);
   }
 };
 
@@ -135,46 +99,29 @@ int run(const Config& cfg, int rank, int size, int ndev) {
 
   T *va = nullptr, *vb = nullptr, *vc = nullptr;
   T *stage_s = nullptr, *stage_r = nullptr; // pinned bounce (staged mode)
-  switch (cfg.alloc) {
-    case 'M':
-      va = (T*)std::malloc(bytes);
-      vb = (T*)std::malloc(bytes);
-      vc = (T*)std::malloc(bytes);
-      break;
-    case 'H':
-      hpk::check_hip(hipHostMalloc((void**)&va, bytes, hipHostMallocDefault), "va");
-      hpk::check_hip(hipHostMalloc((void**)&vb, bytes, hipHostMallocDefault), "vb");
-      hpk::check_hip(hipHostMalloc((void**)&vc, bytes, hipHostMallocDefault), "vc");
-      break;
-    case 'S':
-      hpk::check_hip(hipMallocManaged((void**)&va, bytes, hipMemAttachGlobal), "va");
-      hpk::check_hip(hipMallocManaged((void**)&vb, bytes, hipMemAttachGlobal), "vb");
-      hpk::check_hip(hipMallocManaged((void**)&vc, bytes, hipMemAttachGlobal), "vc");
-      break;
-    case 'D':
-      hpk::check_hip(hipMalloc((void**)&va, bytes), "va");
-      hpk::check_hip(hipMalloc((void**)&vb, bytes), "vb");
-      hpk::check_hip(hipMalloc((void**)&vc, bytes), "vc");
-      hpk::check_hip(hipHostMalloc((void**)&stage_s, bytes,
-                                   hipHostMallocDefault), "stage_s");
-      hpk::check_hip(hipHostMalloc((void**)&stage_r, bytes,
-                                   hipHostMallocDefault), "stage_r");
-      break;
-    default:
-      std::abort();
+  va = (T*)alloc_buf(cfg.alloc, bytes);
+  vb = (T*)alloc_buf(cfg.alloc, bytes);
+  vc = (T*)alloc_buf(cfg.alloc, bytes);
+  if (staged) {
+    stage_s = (T*)alloc_buf('H', bytes);
+    stage_r = (T*)alloc_buf('H', bytes);
   }
   if (!va || !vb || !vc) {
     std::fprintf(stderr, "allocation failed\n");
     MPI_Abort(MPI_COMM_WORLD, 1);
   }
 
+  // device ops run on the null stream and are synchronised at once: MPI
+  // reads the buffer next
   auto fill = [&](T* p, T v) {
-    if (on_gpu) DevOps<T>::fill(p, v, n);
-    else HostOps<T>::fill(p, v, n);
+    if (!on_gpu) return HostOps<T>::fill(p, v, n);
+    hpk::launch_fill(p, v, n, nullptr);
+    hpk::check_hip(hipStreamSynchronize(nullptr), "fill sync");
   };
   auto acc = [&](T* d, const T* s) {
-    if (on_gpu) DevOps<T>::acc(d, s, n);
-    else HostOps<T>::acc(d, s, n);
+    if (!on_gpu) return HostOps<T>::acc(d, s, n);
+    hpk::launch_acc(d, s, n, nullptr);
+    hpk::check_hip(hipStreamSynchronize(nullptr), "acc sync");
   };
 
   int right = (rank + 1) % size;
@@ -229,32 +176,20 @@ int run(const Config& cfg, int rank, int size, int ndev) {
   check_mpi(MPI_Allreduce(&best, &max_time, 1, MPI_DOUBLE, MPI_MAX,
                           MPI_COMM_WORLD), "time max");
 
-  // analytic oracle: every element == size*(size-1)/2
-  double expected = (double)n * ((double)size * (size - 1) / 2.0);
-  double got = on_gpu ? DevOps<T>::sum(vc, n) : HostOps<T>::sum(vc, n);
-  bool pass = std::abs(got - expected) < 1e-6 * std::max(1.0, expected);
-  std::printf("%s rank %d (sum %.1f, expected %.1f)\n",
-              pass ? "Passed" : "FAILED", rank, got, expected);
+  double got = on_gpu ? hpk::reduce_sum(vc, n, nullptr) : HostOps<T>::sum(vc, n);
+  bool pass = hpk_app::allreduce_verdict(got, n, size, rank);
 
   if (rank == 0) {
-    double gb = (double)bytes / 1e9;
-    double busbw =
-        size > 1 ? 2.0 * (size - 1) / size * gb / max_time : gb / max_time;
+    double busbw = hpk_app::allreduce_busbw(bytes, size, max_time);
     std::printf("# mpi algo=%s dtype=%s ranks=%d elems=2^%d alloc=%c "
                 "ndev=%d time=%.6fs busbw=%.2f GB/s\n",
                 cfg.native ? "allreduce" : "ring", cfg.dtype.c_str(), size,
                 cfg.p, cfg.alloc, ndev, max_time, busbw);
   }
 
-  if (cfg.alloc == 'M') {
-    std::free(va); std::free(vb); std::free(vc);
-  } else if (cfg.alloc == 'H') {
-    (void)hipHostFree(va); (void)hipHostFree(vb); (void)hipHostFree(vc);
-  } else {
-    (void)hipFree(va); (void)hipFree(vb); (void)hipFree(vc);
-    if (stage_s) (void)hipHostFree(stage_s);
-    if (stage_r) (void)hipHostFree(stage_r);
-  }
+  for (T* p : {va, vb, vc}) free_buf(cfg.alloc, p);
+  free_buf('H', stage_s);
+  free_buf('H', stage_r);
   return pass ? 0 : 2;
 }
 
@@ -269,10 +204,7 @@ int main(int argc, char* argv[]) {
   Config cfg;
   for (int i = 1; i < argc; ++i) {
     std::string s = argv[i];
-    auto next = [&]() -> const char* {
-      if (++i >= argc) { std::fprintf(stderr, "missing value\n"); std::exit(1); }
-      return argv[i];
-    };
+    auto next = [&] { return hpk_app::next_arg(i, argc, argv); };
     if (s == "-p") cfg.p = std::atoi(next());
     else if (s == "-M") cfg.alloc = 'M';
     else if (s == "-D") cfg.alloc = 'D';

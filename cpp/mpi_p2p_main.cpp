@@ -24,6 +24,7 @@
 
 #include "../hpc_patterns_amd/native/include/hpk.h"
 #include "../hpc_patterns_amd/native/include/mpi_datatype.h"
+#include "miniapp_util.h"
 
 #include <mpi.h>
 
@@ -34,8 +35,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -44,12 +43,7 @@ namespace {
 constexpr size_t kDefaultN = 47185920; // reference peer2pear.cpp:115
 constexpr int kIters = 10;
 
-void check_mpi(int rc, const char* what) {
-  if (rc != MPI_SUCCESS) {
-    std::fprintf(stderr, "MPI error in %s: %d\n", what, rc);
-    MPI_Abort(MPI_COMM_WORLD, 1);
-  }
-}
+using hpk::check_mpi;
 
 unsigned long now_ns() {
   return (unsigned long)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -68,34 +62,20 @@ struct Buffers {
     n = n_;
     alloc = kind;
     size_t bytes = n * sizeof(float);
-    switch (kind) {
-      case 'M': buf = (float*)std::malloc(bytes); break;
-      case 'H':
-        hpk::check_hip(hipHostMalloc((void**)&buf, bytes,
-                                     hipHostMallocDefault), "pinned");
-        break;
-      case 'D':
-        hpk::check_hip(hipMalloc((void**)&dev, bytes), "device");
-        hpk::check_hip(hipHostMalloc((void**)&buf, bytes,
-                                     hipHostMallocDefault), "stage");
-        break;
-      default: std::abort();
-    }
+    // -D: device buffer plus a pinned stage that MPI sees
+    if (kind == 'D') dev = (float*)hpk_app::alloc_buf('D', bytes);
+    buf = (float*)hpk_app::alloc_buf(kind == 'D' ? 'H' : kind, bytes);
     if (!buf) { std::fprintf(stderr, "alloc failed\n"); std::exit(1); }
   }
 
   // reference fill_randomly (peer2pear.cpp:8-17): shuffled iota + checksum
   void fill_payload(unsigned seed) {
-    std::vector<float> v(n);
-    std::iota(v.begin(), v.end(), 0.f);
-    std::minstd_rand g(seed);
-    std::shuffle(v.begin(), v.end(), g);
-    std::memcpy(buf, v.data(), n * sizeof(float));
+    hpk_app::Payload p = hpk_app::shuffled_iota(n, seed);
+    std::memcpy(buf, p.v.data(), n * sizeof(float));
     if (alloc == 'D')
       hpk::check_hip(hipMemcpy(dev, buf, n * sizeof(float),
                                hipMemcpyHostToDevice), "payload h2d");
-    sum = 0.0;
-    for (size_t i = 0; i < n; ++i) sum += (double)v[i];
+    sum = p.sum;
   }
 
   // staged mode: the timed region moves device->stage before the send and
@@ -286,10 +266,7 @@ int main(int argc, char* argv[]) {
   int pipeline = 0;
   for (int i = 1; i < argc; ++i) {
     std::string s = argv[i];
-    auto next = [&]() -> const char* {
-      if (++i >= argc) { std::fprintf(stderr, "missing value\n"); std::exit(1); }
-      return argv[i];
-    };
+    auto next = [&] { return hpk_app::next_arg(i, argc, argv); };
     if (s == "--engine") engine = next();
     else if (s == "-n" || s == "--floats") n = std::strtoull(next(), nullptr, 10);
     else if (s == "-M") alloc = 'M';

@@ -24,6 +24,7 @@
 
 #include "../hpc_patterns_amd/native/include/hpk.h"
 #include "launch_util.h"
+#include "miniapp_util.h"
 
 #include <rccl/rccl.h>
 #include <sys/socket.h>
@@ -31,13 +32,10 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -46,31 +44,16 @@ namespace {
 constexpr size_t kDefaultN = 47185920; // reference peer2pear.cpp:115
 constexpr int kIters = 10;
 
-double now_s() {
-  return std::chrono::duration<double>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
-void check_nccl(ncclResult_t r, const char* what) {
-  if (r != ncclSuccess) {
-    std::fprintf(stderr, "RCCL error in %s: %s\n", what, ncclGetErrorString(r));
-    std::exit(1);
-  }
-}
+using hpk_app::now_s;
+using hpk_launch::check_nccl;
 
 // Host-shuffled iota payload + its exact double checksum.
 double fill_payload(float* dptr, size_t n, unsigned seed) {
-  std::vector<float> v(n);
-  std::iota(v.begin(), v.end(), 0.f);
-  std::minstd_rand g(seed);
-  std::shuffle(v.begin(), v.end(), g);
-  hpk::check_hip(hipMemcpy(dptr, v.data(), n * sizeof(float),
+  hpk_app::Payload p = hpk_app::shuffled_iota(n, seed);
+  hpk::check_hip(hipMemcpy(dptr, p.v.data(), n * sizeof(float),
                            hipMemcpyHostToDevice),
                  "payload H2D");
-  double sum = 0.0;
-  for (size_t i = 0; i < n; ++i) sum += (double)v[i];
-  return sum;
+  return p.sum;
 }
 
 void verify(float* dptr, size_t n, double expected, const char* what) {
@@ -421,10 +404,7 @@ int main(int argc, char* argv[]) {
   int nranks = -1;
   for (int i = 1; i < argc; ++i) {
     std::string s = argv[i];
-    auto next = [&]() -> const char* {
-      if (++i >= argc) { std::fprintf(stderr, "missing value\n"); std::exit(1); }
-      return argv[i];
-    };
+    auto next = [&] { return hpk_app::next_arg(i, argc, argv); };
     if (s == "--probe-ndev") {  // launch_util.h re-exec probe
       std::printf("%d\n", hpk::device_count());
       return 0;

@@ -45,8 +45,9 @@ void launch_busy_wait_mfma(float* out, long tripcount, long n_waves,
 // of hipMemcpyAsync's SDMA path). Pointers may be in any HIP-visible space.
 void launch_copy_kernel(void* dst, const void* src, size_t nbytes,
                         hipStream_t stream);
-// Tunable variant for micro-benchmarking: unroll in {1,4} (16 B vs 64 B per
-// thread per iteration), grid_cap = max workgroups.
+// Tunable variant for micro-benchmarking: unroll 1 or 4 (16 B vs 64 B per
+// thread per iteration), or 5 = the nontemporal 16 B kernel; grid_cap = max
+// workgroups.
 void launch_copy_kernel_tuned(void* dst, const void* src, size_t nbytes,
                               hipStream_t stream, int unroll,
                               size_t grid_cap);
@@ -116,6 +117,27 @@ double reduce_sum_f32(const float* src, size_t n, hipStream_t stream);
 void launch_fill_i32(int* dst, int value, size_t n, hipStream_t stream);
 void launch_acc_i32(int* dst, const int* src, size_t n, hipStream_t stream);
 long long reduce_sum_i32(const int* src, size_t n, hipStream_t stream);
+
+// Typed spellings for C++ callers templated on float|int (the miniapps).
+// The _f32/_i32 names stay the bindings' entry points.
+inline void launch_fill(float* d, float v, size_t n, hipStream_t s) {
+  launch_fill_f32(d, v, n, s);
+}
+inline void launch_fill(int* d, int v, size_t n, hipStream_t s) {
+  launch_fill_i32(d, v, n, s);
+}
+inline void launch_acc(float* d, const float* src, size_t n, hipStream_t s) {
+  launch_acc_f32(d, src, n, s);
+}
+inline void launch_acc(int* d, const int* src, size_t n, hipStream_t s) {
+  launch_acc_i32(d, src, n, s);
+}
+inline double reduce_sum(const float* p, size_t n, hipStream_t s) {
+  return reduce_sum_f32(p, n, s);
+}
+inline double reduce_sum(const int* p, size_t n, hipStream_t s) {
+  return (double)reduce_sum_i32(p, n, s);
+}
 
 // ---------------------------------------------------------------------------
 // Concurrency engine (conc.hip) — reference bench<T>() ABI, bench.hpp:37-40.

@@ -13,6 +13,7 @@
 #include <mpi.h>
 
 #include <cstdint>
+#include <cstdio>
 
 namespace hpk {
 
@@ -34,6 +35,13 @@ template <> struct mpi_datatype<long double> { static MPI_Datatype value() { ret
 template <typename T>
 inline MPI_Datatype get_mpi_datatype() {
   return mpi_datatype<T>::value();
+}
+
+inline void check_mpi(int rc, const char* what) {
+  if (rc != MPI_SUCCESS) {
+    std::fprintf(stderr, "MPI error in %s: %d\n", what, rc);
+    MPI_Abort(MPI_COMM_WORLD, 1);
+  }
 }
 
 } // namespace hpk

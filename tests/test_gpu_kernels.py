@@ -232,6 +232,73 @@ def test_copy_kernel_tuned_unrolled_body(ops, dev, unroll, cap, src_offset):
     assert _canaries_intact(base, dst)
 
 
+@pytest.mark.parametrize("nbytes", [1, 15])
+def test_copy_kernel_aligned_tail_only(ops, dev, nbytes):
+    """16-byte-aligned pointers and fewer than 16 bytes: no 16-byte item,
+    so the generic launcher skips the body and launches the tail alone."""
+    g = torch.Generator(device="cpu").manual_seed(nbytes)
+    src0 = torch.randint(0, 256, (nbytes,), generator=g,
+                         dtype=torch.uint8).to(dev)
+    _, src = _window(dev, nbytes, 0, torch.uint8)
+    base, dst = _window(dev, nbytes, 0, torch.uint8)
+    src.copy_(src0)
+    ops.copy_kernel(dst, src)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src0)
+    assert _canaries_intact(base, dst)
+
+
+@pytest.mark.parametrize("unroll", [1, 4, 5])
+@pytest.mark.parametrize("nbytes", [5, 16, 21])
+def test_copy_kernel_tuned_small_aligned(ops, dev, nbytes, unroll):
+    """Aligned, grid_cap=1: 5 bytes is an empty body launch (n16 == 0, which
+    the tuned launcher does not skip) plus a tail, 16 one item and no tail,
+    21 both."""
+    from hpc_patterns_amd._native import native
+
+    g = torch.Generator(device="cpu").manual_seed(nbytes * 10 + unroll)
+    src0 = torch.randint(0, 256, (nbytes,), generator=g,
+                         dtype=torch.uint8).to(dev)
+    _, src = _window(dev, nbytes, 0, torch.uint8)
+    base, dst = _window(dev, nbytes, 0, torch.uint8)
+    src.copy_(src0)
+    torch.cuda.synchronize()
+    native().copy_kernel_tuned(dst.data_ptr(), src.data_ptr(), nbytes,
+                               torch.cuda.current_stream().cuda_stream,
+                               unroll, 1)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src0)
+    assert _canaries_intact(base, dst)
+
+
+# Smallest size at which the reductions' clamp to 4096 blocks changes the
+# grid (one block's worth past 4096 * 256 * 8) and a ragged end remains.
+_REDUCE_CLAMP_N = 4096 * 256 * 8 + 256 * 8 + 3
+
+
+def test_reduce_sum_i32_above_block_cap(ops, dev):
+    from hpc_patterns_amd._native import native
+
+    n = _REDUCE_CLAMP_N
+    g = torch.Generator(device="cpu").manual_seed(7)
+    host = torch.randint(-2 ** 30, 2 ** 30 + 1, (n,), generator=g,
+                         dtype=torch.int32)
+    t = host.to(dev)
+    got = native().reduce_sum_i32(t.data_ptr(), n,
+                                  torch.cuda.current_stream().cuda_stream)
+    assert got == int(host.long().sum())
+
+
+def test_reduce_sum_above_block_cap(ops, dev):
+    """Integer-valued addends, as in test_reduce_sum_tails_and_misaligned:
+    every partial sum is an exact double, so the result must be equal."""
+    n = _REDUCE_CLAMP_N
+    g = torch.Generator(device="cpu").manual_seed(8)
+    host = torch.randint(-1000, 1001, (n,), generator=g)
+    got = ops.reduce_sum(host.float().to(dev))
+    assert got == float(int(host.sum()))
+
+
 # The nontemporal streaming kernels (copy, fill, accumulate) cap their grid
 # at 131072 blocks of 256 threads, one 16-byte item per thread per
 # iteration — so they grid-stride only above 512 MiB, the regime of the
