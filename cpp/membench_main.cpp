@@ -80,6 +80,33 @@ int main(int argc, char* argv[]) {
   std::printf("%-26s %8.3f ms %9.1f GB/s read\n", "reduce_sum (exact f64)",
               t * 1e3, bytes / t / 1e9);
 
+  // MX quantize (quant.hip): n elements in `a` (fp32, or its first half
+  // read as bf16) -> codes at the start of `b`, scale bytes behind them.
+  // Rate = all bytes moved (input + codes + scales), to set beside twice
+  // the copy kernel's payload rate above.
+  {
+    const long qrows = (long)(n / 32); // flat: one 32-block per row
+    const size_t nq = (size_t)qrows * 32;
+    char* codes = reinterpret_cast<char*>(b);
+    char* scales = codes + nq; // nq <= bytes / 4: both fit in b
+    struct { const char* name; int bf16, fmt; } cases[] = {
+        {"quantize fp32->mxfp8", 0, hpk::kMxFp8},
+        {"quantize fp32->mxfp4", 0, hpk::kMxFp4},
+        {"quantize bf16->mxfp8", 1, hpk::kMxFp8},
+        {"quantize bf16->mxfp4", 1, hpk::kMxFp4}};
+    for (auto& c : cases) {
+      if (!qrows) break;
+      t = time_best([&] {
+        hpk::launch_quantize_mx(codes, scales, a, c.bf16, c.fmt, qrows, 32,
+                                nullptr);
+      });
+      double moved = nq * ((c.bf16 ? 2.0 : 4.0) +
+                           (c.fmt == hpk::kMxFp4 ? 0.5 : 1.0) + 1.0 / 32);
+      std::printf("%-26s %8.3f ms %9.1f GB/s moved %8.1f Gelem/s\n", c.name,
+                  t * 1e3, moved / t / 1e9, nq / t / 1e9);
+    }
+  }
+
   // busy loops
   long gs = 1 << 20, trip = quick ? 500 : 2000;
   float* out = nullptr;

@@ -119,6 +119,18 @@ PYBIND11_MODULE(_hpk, m) {
         py::arg("kind"), py::arg("m"), py::arg("n"), py::arg("k"),
         "name of the kernel the gemm_<kind>_nt launcher runs at this shape "
         "under the current HPK_* environment");
+  m.attr("QUANT_MAX_GRID") = hpk::kQuantMaxGrid;
+  m.def("quantize_mx",
+        [](uintptr_t q, uintptr_t scale, uintptr_t x, int x_is_bf16, int fmt,
+           long rows, long k, uintptr_t stream) {
+          hpk::launch_quantize_mx(reinterpret_cast<void*>(q),
+                                  reinterpret_cast<void*>(scale),
+                                  reinterpret_cast<const void*>(x), x_is_bf16,
+                                  fmt, rows, k, as_stream(stream));
+        },
+        py::arg("q"), py::arg("scale"), py::arg("x"), py::arg("x_is_bf16"),
+        py::arg("fmt"), py::arg("rows"), py::arg("k"), py::arg("stream") = 0,
+        "fmt: 0 = mxfp8 (e4m3 bytes), 1 = mxfp4 (packed e2m1 nibbles)");
   m.def("copy_kernel",
         [](uintptr_t dst, uintptr_t src, size_t nbytes, uintptr_t stream) {
           hpk::launch_copy_kernel(reinterpret_cast<void*>(dst),

@@ -108,6 +108,23 @@ void launch_gemm_mxfp4_nt(float* C, const void* A, const void* B,
 // switch on the same decision; illegal shapes and unknown kinds throw.
 const char* gemm_variant_name(const char* kind, long M, long N, long K);
 
+// MX quantize (quant.hip): the convert-to-MX step that makes the two MX
+// GEMMs' operands from real data. x is [rows][K] contiguous fp32 (or bf16
+// when x_is_bf16), K % 32 == 0; every 32 consecutive elements along K get
+// one e8m0 scale byte (scale: uint8 [rows][K/32]) and are rounded to
+// nearest-even, saturating, into q: fmt kMxFp8 -> e4m3 bytes [rows][K],
+// fmt kMxFp4 -> e2m1 nibbles [rows][K/2], low nibble = even k. Bit-exact
+// contract: docs/gemm.md. x and q 16-byte aligned, scale 4-byte aligned
+// (throws otherwise). Grid-stride above kQuantMaxGrid workgroups.
+enum { kMxFp8 = 0, kMxFp4 = 1 };
+// 8 resident 256-thread blocks per CU. Measured at 1 GiB (profiles/
+// membench_quantize.log): caps of 32768 and up run 6-13% faster, but then
+// the grid-stride pass only starts beyond 1 GiB of fp32 input, out of reach
+// of a quick test; 2048 keeps it testable at 64 MiB.
+constexpr size_t kQuantMaxGrid = 2048;
+void launch_quantize_mx(void* q, void* scale, const void* x, int x_is_bf16,
+                        int fmt, long rows, long K, hipStream_t stream);
+
 // Exact double-precision sum of n floats. Synchronizes `stream`.
 // Replaces the reference's O(N log N) host sort+sum checksum
 // (peer2pear.cpp:56-63) with an order-independent exact device reduction.

@@ -391,3 +391,150 @@ def matmul_nt(a: torch.Tensor, b: torch.Tensor,
     if (mp, np_) == (m, n):
         return c
     return c[:m, :n].contiguous()
+
+
+# ---------------------------------------------------------------------------
+# MX quantize: the convert-to-MX step (OCP MX v1.0 §6.3) in front of
+# gemm_mxfp8 / gemm_mxfp4. Contract: docs/gemm.md, "MX quantize".
+# ---------------------------------------------------------------------------
+
+# fmt -> (native format code, emax of the element format, largest magnitude)
+_MX_FORMATS = {"mxfp8": (0, 8, 448.0), "mxfp4": (1, 2, 6.0)}
+
+# midpoints between adjacent e2m1 magnitudes (0, .5, 1, 1.5, 2, 3, 4, 6)
+_E2M1_MIDPOINTS = [0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0]
+
+
+def _mx_format(fmt):
+    if fmt not in _MX_FORMATS:
+        raise ValueError(f"unknown MX format {fmt!r}; expected one of "
+                         f"{sorted(_MX_FORMATS)}")
+    return _MX_FORMATS[fmt]
+
+
+def _pow2_f64(exponent: torch.Tensor) -> torch.Tensor:
+    """2.0 ** exponent as float64, built from the bits (exact on any
+    device). exponent: integer tensor within the float64 normal range."""
+    return ((exponent.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def quantize_mx_reference(x: torch.Tensor, fmt: str):
+    """Pure-torch oracle of quantize_mx, on whatever device x lives on.
+
+    Same contract and same (q, scale) layouts, bit for bit. The scaling is
+    done in float64, where v * 2^(127 - s) is exact for every fp32 v, and
+    the value is clamped and rounded to the element grid (nearest, ties to
+    the even code) before the final cast, so that cast is exact and no
+    device's conversion rules enter the result.
+    """
+    _, emax, vmax = _mx_format(fmt)
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("x must be a 2-D float32 or bfloat16 tensor")
+    rows, k = x.shape
+    if k % 32 != 0:
+        raise ValueError(f"K = {k} is not a multiple of 32")
+    xf = x.float().contiguous()          # bf16 -> fp32 is exact
+    field = (xf.view(torch.int32) >> 23) & 0xFF
+    e = field.view(rows, k // 32, 32).amax(-1)
+    scale = torch.where(e == 255, torch.full_like(e, 255),
+                        (e - emax).clamp_min(0))
+    v = xf.double()
+    # exponent field 0 (zeros and fp32 subnormals) -> zero, sign kept
+    v = torch.where(field == 0, torch.copysign(torch.zeros_like(v), v), v)
+    y = v.view(rows, k // 32, 32) * _pow2_f64(127 - scale).unsqueeze(-1)
+    y = y.clamp(-vmax, vmax).view(rows, k)
+    if fmt == "mxfp8":
+        # e4m3 grid: 3 mantissa bits, smallest normal exponent -6, below it
+        # the subnormal step 2^-9. torch.round rounds half to even, and an
+        # even multiple of the step is the code with the even mantissa.
+        _, ex = torch.frexp(y)                      # |y| in [2^(ex-1), 2^ex)
+        step = _pow2_f64((ex - 1).clamp_min(-6) - 3)
+        y = torch.round(y / step) * step            # keeps the sign of zero
+        q = y.float().to(torch.float8_e4m3fn)
+    else:
+        # midpoint bucketing; a tie goes to the code with the even index:
+        # 0.25->0, 0.75->1, 1.25->1, 1.75->2, 2.5->2, 3.5->4, 5->4
+        mag = y.abs()
+        idx = torch.zeros_like(mag, dtype=torch.uint8)
+        for i, mid in enumerate(_E2M1_MIDPOINTS):
+            idx += ((mag > mid) if i % 2 == 0 else (mag >= mid)).to(torch.uint8)
+        nib = idx | (torch.signbit(y).to(torch.uint8) << 3)
+        q = (nib[:, 0::2] | (nib[:, 1::2] << 4)).contiguous()
+    return q, scale.to(torch.uint8)
+
+
+def dequantize_mx(q: torch.Tensor, scale: torch.Tensor, fmt: str) -> torch.Tensor:
+    """float64 value of an MX tensor: element * 2^(scale - 127) per 32-block
+    along K; a block whose scale byte is 255 (e8m0 NaN) is all NaN.
+    Reference only — pure torch."""
+    _mx_format(fmt)
+    v = q.float().double() if fmt == "mxfp8" else e2m1_decode(q).double()
+    rows, k = v.shape
+    if scale.shape != (rows, k // 32) or scale.dtype != torch.uint8:
+        raise ValueError("scale must be uint8 [rows, K//32]")
+    s = scale.to(torch.int64)
+    factor = torch.where(s == 255, torch.full_like(s, 0, dtype=torch.float64)
+                         + float("nan"), _pow2_f64(s - 127))
+    return (v.view(rows, k // 32, 32) * factor.unsqueeze(-1)).view(rows, k)
+
+
+def quantize_mx(x: torch.Tensor, fmt: str, stream=None):
+    """Convert-to-MX on the GPU (native/quant.hip): fp32 or bf16 [rows, K]
+    -> (q, scale), exactly the operands gemm_mxfp8 / gemm_mxfp4 take.
+
+    One e8m0 scale byte per 32 consecutive elements along K, scale =
+    max(largest exponent field of the block - emax, 0) (255 if the block
+    holds an Inf or NaN); elements scaled by 2^(127 - scale), saturated to
+    +-448 / +-6 and rounded to nearest-even. "mxfp8": q is float8_e4m3fn
+    [rows, K]; "mxfp4": q is uint8 [rows, K//2], low nibble = even k (the
+    e2m1_pack layout). scale is uint8 [rows, K//32]. Full contract:
+    docs/gemm.md. K must be a multiple of 32 (matmul_mx pads).
+    """
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise TypeError("x must be a CUDA tensor")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise TypeError("x must be a contiguous 2-D tensor")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"x must be float32 or bfloat16, got {x.dtype}")
+    code, _, _ = _mx_format(fmt)
+    rows, k = x.shape
+    if rows < 1 or k < 32 or k % 32 != 0:
+        raise ValueError(f"need rows >= 1 and K a positive multiple of 32; "
+                         f"got {tuple(x.shape)}")
+    if x.data_ptr() % 16 != 0:
+        raise ValueError("x must start on a 16-byte boundary (the kernel "
+                         "reads it with 16-byte loads)")
+    if fmt == "mxfp8":
+        q = torch.empty(rows, k, dtype=torch.float8_e4m3fn, device=x.device)
+    else:
+        q = torch.empty(rows, k // 2, dtype=torch.uint8, device=x.device)
+    scale = torch.empty(rows, k // 32, dtype=torch.uint8, device=x.device)
+    native().quantize_mx(q.data_ptr(), scale.data_ptr(), x.data_ptr(),
+                         int(x.dtype == torch.bfloat16), code, rows, k,
+                         _stream_handle(stream))
+    return q, scale
+
+
+def matmul_mx(a: torch.Tensor, b: torch.Tensor, fmt: str = "mxfp8",
+              stream=None) -> torch.Tensor:
+    """A @ B^T through the MX GEMMs from real tensors: a [M,K], b [N,K],
+    fp32 or bf16, any M, N, K; returns fp32 [M,N].
+
+    K is zero-padded up to a multiple of 32 (zeros change no block
+    maximum), both operands go through quantize_mx, and matmul_nt does
+    the tile padding and picks the kernel.
+    """
+    _mx_format(fmt)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"need A[M,K], B[N,K]; got A{tuple(a.shape)} "
+                         f"B{tuple(b.shape)}")
+    k = a.shape[1]
+    kp = -(-k // 32) * 32
+    def operand(t):
+        t = _pad2d(t.contiguous(), t.shape[0], kp)
+        # a contiguous view may start off a 16-byte boundary; a copy does not
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+
+    aq, a_scale = quantize_mx(operand(a), fmt, stream=stream)
+    bq, b_scale = quantize_mx(operand(b), fmt, stream=stream)
+    return matmul_nt(aq, bq, a_scale, b_scale, stream=stream)

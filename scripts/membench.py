@@ -33,9 +33,43 @@ def time_gpu(fn, reps=5, warmup=2):
     return best
 
 
+def quantize_section(hpk, dev, quick):
+    """MX quantize (native/quant.hip) next to the K2 nontemporal copy of the
+    same run. Both as HBM traffic: the copy moves 2x its payload, a quantize
+    row its input plus the codes plus one scale byte per 32 elements."""
+    import torch
+
+    from hpc_patterns_amd import ops
+
+    rows = 4096 if quick else 16384     # x 16384: 256 MiB / 1 GiB of fp32,
+    k = 16384                           # at or beyond the 256 MiB LLC
+    n = rows * k
+    print(f"\n# MX quantize, [{rows}, {k}] = {n} elements (total HBM bytes "
+          "moved; copy = 2x payload)")
+    x32 = torch.randn(rows, k, device=dev)
+    dst = torch.empty_like(x32)
+    s = torch.cuda.current_stream().cuda_stream
+    t = time_gpu(lambda: hpk.copy_kernel_tuned(
+        dst.data_ptr(), x32.data_ptr(), n * 4, s, 5, 131072))
+    copy_rate = 2 * n * 4 / t
+    print(f"{'K2 copy (NT, fp32 bytes)':>26} {t*1e3:9.3f} ms "
+          f"{copy_rate/1e9:9.1f} GB/s moved")
+    del dst
+    x16 = x32.bfloat16()
+    for name, x, in_b in (("fp32", x32, 4), ("bf16", x16, 2)):
+        for fmt, q_b in (("mxfp8", 1.0), ("mxfp4", 0.5)):
+            t = time_gpu(lambda: ops.quantize_mx(x, fmt))
+            moved = n * (in_b + q_b + 1 / 32)
+            print(f"{'quantize ' + name + '->' + fmt:>26} {t*1e3:9.3f} ms "
+                  f"{moved/t/1e9:9.1f} GB/s moved {n/t/1e9:8.1f} Gelem/s "
+                  f"{moved/t/copy_rate:6.2f} x copy", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--quantize-only", action="store_true",
+                    help="only the MX quantize rows (and their copy row)")
     args = ap.parse_args()
 
     import torch
@@ -45,6 +79,10 @@ def main():
     hpk = native()
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
+
+    if args.quantize_only:
+        quantize_section(hpk, dev, args.quick)
+        return
 
     sizes = [64 << 20, 256 << 20, 1 << 30] if not args.quick else [64 << 20]
     print("# shader-copy sweep: payload GB/s (bytes moved = 2x payload)")
@@ -84,6 +122,9 @@ def main():
     print(f"acc (NT)    {t*1e3:9.3f} ms  {3*n*4/t/1e9:9.1f} GB/s (2r+1w)")
     t = time_gpu(lambda: hpk.reduce_sum_f32(a.data_ptr(), n, s))
     print(f"reduce_sum  {t*1e3:9.3f} ms  {n*4/t/1e9:9.1f} GB/s (read)")
+
+    del a, b
+    quantize_section(hpk, dev, args.quick)
 
     print("\n# busy_wait FMA rate (globalsize 1M, tripcount 2000)")
     out = torch.empty(1 << 20, dtype=torch.float32, device=dev)
