@@ -26,7 +26,8 @@ LIB_SRCS   := $(NATIVE)/kernels.hip $(NATIVE)/quant.hip $(NATIVE)/gemm.hip $(NAT
 LIB_OBJS   := $(patsubst $(NATIVE)/%.hip,$(BUILD)/%.o,$(LIB_SRCS))
 
 EXT_SO     := hpc_patterns_amd/_hpk$(EXT_SUFFIX)
-BINARIES   := $(BIN)/hpk_conc $(BIN)/hpk_topology $(BIN)/hpk_allreduce $(BIN)/hpk_p2p $(BIN)/hpk_interop $(BIN)/hpk_membench
+BINARIES   := $(BIN)/hpk_conc $(BIN)/hpk_topology $(BIN)/hpk_allreduce $(BIN)/hpk_p2p $(BIN)/hpk_interop $(BIN)/hpk_membench $(BIN)/hpk_push_pool
+HOSTCXX    ?= g++
 
 # Real-MPI twins (MPICH 3.3.2 ships in /opt/conda — not GPU-aware, so the
 # miniapps use pinned-direct / staged-device buffer modes; see PARITY.md).
@@ -52,6 +53,7 @@ $(BUILD)/%.o: $(NATIVE)/%.hip $(NATIVE)/include/hpk.h | $(BUILD)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 $(BUILD)/sdma.o $(BUILD)/step.o: $(NATIVE)/include/sdma_route.h
+$(BUILD)/step.o: $(NATIVE)/include/push_pool.h
 
 $(BUILD)/ext.o: $(NATIVE)/ext.cpp $(NATIVE)/include/hpk.h | $(BUILD)
 	$(HIPCC) $(CXXFLAGS) -I$(PY_INC) -I$(PYBIND_INC) -c $< -o $@
@@ -81,6 +83,15 @@ $(BIN)/hpk_interop: $(BUILD)/interop_main.o $(LIB_OBJS) | $(BIN)
 
 $(BIN)/hpk_membench: $(BUILD)/membench_main.o $(LIB_OBJS) | $(BIN)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) $^ -o $@ $(LDFLAGS)
+
+# StepPlan's push workers alone, on host memory: host compiler, no HIP
+$(BIN)/hpk_push_pool: cpp/push_pool_main.cpp $(NATIVE)/include/push_pool.h | $(BIN)
+	$(HOSTCXX) -O2 -std=c++17 -Wall -pthread $< -o $@
+
+# the same program under ThreadSanitizer, built and run (CPU only)
+tsan-push: | $(BUILD)
+	$(HOSTCXX) -O1 -g -std=c++17 -Wall -pthread -fsanitize=thread cpp/push_pool_main.cpp -o $(BUILD)/hpk_push_pool_tsan
+	$(BUILD)/hpk_push_pool_tsan
 
 # dedicated rule (NOT a target-specific CXXFLAGS append: `make asan`
 # overrides CXXFLAGS on the command line, which would drop the append) —
@@ -119,4 +130,4 @@ gpu-test:
 clean:
 	rm -rf $(BUILD) $(BIN) $(EXT_SO)
 
-.PHONY: asan clean-bins test gpu-test
+.PHONY: asan clean-bins test gpu-test tsan-push

@@ -17,9 +17,13 @@ The four local commands are submitted and joined by one native object
 resolved once with the device idle, both engine copies go out back to back
 and ahead of the kernels, and the join spins on the two signals. The
 device-wide sync after the join stays: it measured 5 us on an already-idle
-device (profiles/flagship_link_idle.md). HPK_STEP_PLAN=0 keeps the earlier
-one-call-per-command path (sdma_copy_begin/sdma_wait), which is also what
-calibration and measure_overlap's serial leg use.
+device (profiles/flagship_link_idle.md). The plan also moves the tail of
+H2D with host threads storing through the PCIe BAR, where the machine
+allows it, which shortens D2H (profiles/flagship_host_push.md); it reads
+HPK_STEP_PUSH (0 = off, or a fixed fraction) and HPK_STEP_PUSH_THREADS
+itself, and step.plan.push_fraction says what it chose. HPK_STEP_PLAN=0
+keeps the earlier one-call-per-command path (sdma_copy_begin/sdma_wait),
+which is also what calibration and measure_overlap's serial leg use.
 
 The benchmark value is whole-job aggregate bandwidth: payload bytes moved by
 all ranks divided by step time (max over ranks). Compute contributes no

@@ -305,7 +305,7 @@ PYBIND11_MODULE(_hpk, m) {
                        std::tuple<uintptr_t, uintptr_t, size_t> d2d,
                        uintptr_t busy_out, long busy_globalsize,
                        uintptr_t busy_stream, uintptr_t copy_stream,
-                       bool time_copies) {
+                       bool time_copies, double push_fraction) {
              auto triple = [](const std::tuple<uintptr_t, uintptr_t, size_t>& t) {
                return hpk::StepCopy{reinterpret_cast<void*>(std::get<0>(t)),
                                     reinterpret_cast<const void*>(std::get<1>(t)),
@@ -315,13 +315,16 @@ PYBIND11_MODULE(_hpk, m) {
                                       triple(d2d),
                                       reinterpret_cast<float*>(busy_out),
                                       busy_globalsize, as_stream(busy_stream),
-                                      as_stream(copy_stream), time_copies);
+                                      as_stream(copy_stream), time_copies,
+                                      push_fraction);
            }),
            py::arg("device"), py::arg("h2d"), py::arg("d2h"), py::arg("d2d"),
            py::arg("busy_out"), py::arg("busy_globalsize"),
            py::arg("busy_stream"), py::arg("copy_stream"),
-           py::arg("time_copies") = false,
-           "h2d/d2h/d2d are (dst, src, nbytes) triples of raw pointers")
+           py::arg("time_copies") = false, py::arg("push_fraction") = -1.0,
+           "h2d/d2h/d2d are (dst, src, nbytes) triples of raw pointers; "
+           "push_fraction < 0 leaves the host-push share of H2D to "
+           "HPK_STEP_PUSH or the plan's own calibration")
       .def("submit", &hpk::StepPlan::submit, py::arg("tripcount"),
            py::call_guard<py::gil_scoped_release>())
       .def("join", &hpk::StepPlan::join,
@@ -333,7 +336,25 @@ PYBIND11_MODULE(_hpk, m) {
            [](const hpk::StepPlan& p) { return p.copy_times(); },
            "[(start_ns, end_ns), ...] per engine copy, H2D then D2H per "
            "submission; empty unless time_copies")
-      .def("clear_copy_times", &hpk::StepPlan::clear_copy_times);
+      .def("clear_copy_times", &hpk::StepPlan::clear_copy_times)
+      .def_property_readonly("push_fraction", &hpk::StepPlan::push_fraction)
+      .def_property_readonly("push_threads", &hpk::StepPlan::push_threads)
+      .def_property_readonly("push_access", &hpk::StepPlan::push_access)
+      .def("push_times", &hpk::StepPlan::push_times,
+           "(wake_ns, done_ns) of the last joined step's workers, from "
+           "submit entry; zeros unless time_copies")
+      .def("push_probe", &hpk::StepPlan::push_probe, py::arg("reps") = 5,
+           py::call_guard<py::gil_scoped_release>(),
+           "[(name, value), ...]: BAR access, push rates, D2H under push "
+           "(scripts/step_push_probe.py)");
+  m.def("step_push_ranges",
+        [](size_t nbytes, double g, int nthreads) {
+          hpk::StepPushSplit s = hpk::step_push_ranges(nbytes, g, nthreads);
+          return py::make_tuple(s.head, s.ranges);
+        },
+        py::arg("nbytes"), py::arg("g"), py::arg("nthreads"),
+        "(head, [(begin, end), ...]): the engine's share of an H2D copy and "
+        "the push workers' ranges; pure host function");
   m.def("hsa_timestamp_ns", &hpk::hsa_timestamp_ns);
   m.def("trace_push", [](const std::string& n) { hpk::trace_push(n.c_str()); });
   m.def("trace_pop", &hpk::trace_pop);

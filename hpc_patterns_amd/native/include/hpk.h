@@ -277,35 +277,88 @@ struct StepCopy {
   size_t nbytes = 0;
 };
 
+// Below this H2D size the plan does not choose a push fraction by itself:
+// waking the workers costs about what 2 % of the copy would save.
+constexpr size_t kStepPushMinBytes = size_t(16) << 20;
+// Push workers when HPK_STEP_PUSH_THREADS is not set: the smallest count at
+// which the measured push rate stops rising (profiles/flagship_host_push.md).
+constexpr int kStepPushDefaultThreads = 8;
+
+// Host push (step.hip, include/push_pool.h). An engine-driven H2D is a
+// stream of device reads whose requests travel host-bound, next to the D2H
+// payload; bytes that the host stores straight into device memory (posted
+// writes through the PCIe BAR) need none. The plan can therefore give the
+// tail [head, nbytes) of its H2D copy to a pool of host threads and leave
+// the head on the engine. Where the head ends and which thread stores what:
+struct StepPushSplit {
+  size_t head = 0;                               // engine copies [0, head)
+  std::vector<std::pair<size_t, size_t>> ranges; // [begin, end) per thread
+};
+// Pure host function. head = (1 - g) * nbytes rounded down to 4 KiB; the
+// ranges tile [head, nbytes) in order, each beginning on a 64-byte line and
+// only the last non-empty one ending off a line; threads left without a
+// line get an empty range. g <= 0: head == nbytes; g >= 1: head == 0.
+StepPushSplit step_push_ranges(size_t nbytes, double g, int nthreads);
+
 class StepPlan {
  public:
   // Construct with the device idle (the engine status query reports only
   // idle engines). Throws if the H2D and D2H copies do not resolve to two
   // distinct host SDMA engines. time_copies turns on ROCr's async-copy
-  // profiling for the life of the plan (diagnostic; off in normal use).
+  // profiling for the life of the plan and records the workers' times
+  // (diagnostic; off in normal use).
+  //
+  // push_fraction is g, the share of H2D that host threads store:
+  //   < 0  (default) — HPK_STEP_PUSH if set (0 = off, else the fraction);
+  //        otherwise chosen once, here, from three times measured on the
+  //        plan's own buffers (engine H2D alone, engine D2H alone, a pushed
+  //        slice of up to 32 MiB) — which runs both copies once — and only
+  //        for an H2D of kStepPushMinBytes or more;
+  //   >= 0 — that fraction (1.0 pushes everything; for tests).
+  // Whatever was asked, g is 0 when the CPU agent nearest the device is not
+  // granted access to the H2D destination or the device reports no HDP
+  // flush register. Thread count: HPK_STEP_PUSH_THREADS, 1..8.
   StepPlan(int device, StepCopy h2d, StepCopy d2h, StepCopy d2d,
            float* busy_out, long busy_globalsize, hipStream_t busy_stream,
-           hipStream_t copy_stream, bool time_copies = false);
+           hipStream_t copy_stream, bool time_copies = false,
+           double push_fraction = -1.0);
   ~StepPlan();
   StepPlan(const StepPlan&) = delete;
   StepPlan& operator=(const StepPlan&) = delete;
 
-  // H2D, D2H (engines), then busy-wait and shader-copy kernels (streams).
-  // Throws if the previous submission was not joined; that submission
-  // stays joinable.
+  // Wakes the push workers, then H2D head, D2H (engines), then busy-wait
+  // and shader-copy kernels (streams). Throws if the previous submission was
+  // not joined; that submission stays joinable.
   void submit(long tripcount);
-  // Waits for both copies, then synchronizes both kernel streams. Returns
-  // at once when nothing is pending.
+  // Waits for the workers and flushes the HDP so the device sees what they
+  // stored, waits for both copies, then synchronizes both kernel streams.
+  // Returns at once when nothing is pending.
   void join();
-  // join() if pending, then destroy the signals. Idempotent.
+  // join() if pending, then end the workers and destroy the signals.
+  // Idempotent.
   void close();
   bool pending() const;
 
   // (start_ns, end_ns) of every engine copy joined so far, H2D then D2H
-  // per submission, on the hsa_timestamp_ns() clock. Empty unless
-  // time_copies was set.
+  // per submission, on the hsa_timestamp_ns() clock; (0, 0) for an H2D
+  // that was pushed whole. Empty unless time_copies was set.
   const std::vector<std::pair<uint64_t, uint64_t>>& copy_times() const;
   void clear_copy_times();
+
+  // What the plan chose.
+  double push_fraction() const; // tail bytes / H2D bytes after rounding
+  int push_threads() const;     // 0 when nothing is pushed
+  bool push_access() const;     // CPU access granted and HDP flush present
+  // Last joined step, time_copies only, else zeros: submit() entry to the
+  // first worker's first store, and to the last worker's fence, in ns.
+  std::pair<uint64_t, uint64_t> push_times() const;
+
+  // Measurements behind profiles/flagship_host_push.md, on this plan's
+  // buffers, copies only (no kernels): BAR access, push rate for 1/2/4/8
+  // threads at 32 and 128 MiB, and the D2H engine time alone, next to the
+  // engine H2D, next to a push of all of H2D and next to each g-split.
+  // (name, value) rows; times in us, rates in GB/s. Nothing may be pending.
+  std::vector<std::pair<std::string, double>> push_probe(int reps = 5);
 
  private:
   struct Impl;
