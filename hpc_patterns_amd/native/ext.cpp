@@ -119,6 +119,62 @@ PYBIND11_MODULE(_hpk, m) {
         py::arg("kind"), py::arg("m"), py::arg("n"), py::arg("k"),
         "name of the kernel the gemm_<kind>_nt launcher runs at this shape "
         "under the current HPK_* environment");
+  m.def("gemm_splitk_bf16_nt",
+        [](uintptr_t c, uintptr_t a, uintptr_t b, long m, long n, long k,
+           int splits, uintptr_t workspace, uintptr_t stream,
+           int xcd_swizzle) {
+          hpk::launch_gemm_splitk_bf16_nt(
+              reinterpret_cast<float*>(c), reinterpret_cast<const void*>(a),
+              reinterpret_cast<const void*>(b), m, n, k, splits,
+              reinterpret_cast<void*>(workspace), as_stream(stream),
+              xcd_swizzle);
+        },
+        py::arg("c"), py::arg("a"), py::arg("b"), py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("splits"), py::arg("workspace") = 0,
+        py::arg("stream") = 0, py::arg("xcd_swizzle") = 0);
+  m.def("gemm_splitk_fp8_nt",
+        [](uintptr_t c, uintptr_t a, uintptr_t b, long m, long n, long k,
+           int splits, uintptr_t workspace, uintptr_t stream,
+           int xcd_swizzle) {
+          hpk::launch_gemm_splitk_fp8_nt(
+              reinterpret_cast<float*>(c), reinterpret_cast<const void*>(a),
+              reinterpret_cast<const void*>(b), m, n, k, splits,
+              reinterpret_cast<void*>(workspace), as_stream(stream),
+              xcd_swizzle);
+        },
+        py::arg("c"), py::arg("a"), py::arg("b"), py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("splits"), py::arg("workspace") = 0,
+        py::arg("stream") = 0, py::arg("xcd_swizzle") = 0);
+  m.def("gemm_splitk_i8_nt",
+        [](uintptr_t c, uintptr_t a, uintptr_t b, long m, long n, long k,
+           int splits, uintptr_t workspace, uintptr_t stream,
+           int xcd_swizzle) {
+          hpk::launch_gemm_splitk_i8_nt(
+              reinterpret_cast<int*>(c), reinterpret_cast<const void*>(a),
+              reinterpret_cast<const void*>(b), m, n, k, splits,
+              reinterpret_cast<void*>(workspace), as_stream(stream),
+              xcd_swizzle);
+        },
+        py::arg("c"), py::arg("a"), py::arg("b"), py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("splits"), py::arg("workspace") = 0,
+        py::arg("stream") = 0, py::arg("xcd_swizzle") = 0);
+  m.def("gemm_splitk_ktiles",
+        [](long t, int splits, int s) {
+          if (t < 1 || splits < 1 || splits > t || s < 0 || s >= splits)
+            throw py::value_error("need 1 <= splits <= T and 0 <= s < splits");
+          hpk::SplitKRange r = hpk::gemm_splitk_ktiles(t, splits, s);
+          return py::make_tuple(r.first, r.count);
+        },
+        py::arg("t"), py::arg("splits"), py::arg("s"),
+        "(first, count): the K-tiles, of T = K / 64, that split s of `splits` "
+        "walks; the function the kernel calls");
+  m.def("gemm_splitk_plan", &hpk::gemm_splitk_plan, py::arg("m"),
+        py::arg("n"), py::arg("k"), py::arg("n_cu"),
+        "automatic split count for an (m, n, k) problem on n_cu compute "
+        "units; pure host function");
+  m.attr("SPLITK_MIN_TILES") = hpk::kSplitKMinTiles;
+  m.attr("SPLITK_MAX_SPLITS") = hpk::kSplitKMaxSplits;
+  m.attr("SPLITK_REDUCE_MAX_GRID") = hpk::kSplitKReduceMaxGrid;
   m.attr("QUANT_MAX_GRID") = hpk::kQuantMaxGrid;
   m.def("quantize_mx",
         [](uintptr_t q, uintptr_t scale, uintptr_t x, int x_is_bf16, int fmt,

@@ -108,6 +108,50 @@ void launch_gemm_mxfp4_nt(float* C, const void* A, const void* B,
 // switch on the same decision; illegal shapes and unknown kinds throw.
 const char* gemm_variant_name(const char* kind, long M, long N, long K);
 
+// Split-K (gemm_splitk.hip): the 128^2-tile GEMM for small M, N and a long
+// K. The grid is (tiles, splits): split s of a tile walks only its own
+// K-tiles and writes a 128x128 partial to slice s of `workspace`
+// ([splits][M][N], C's element type, 16-byte aligned); a second kernel on
+// the same stream then folds the slices in ascending s,
+//   C = ((P0 + P1) + P2) + ...,
+// so the result is the same bits on every run. splits == 1 writes C
+// directly: no workspace, no second kernel. Contract: docs/gemm.md.
+//
+// Which K-tiles (of T = K / 64) split s of S owns: T / S + (s < T % S)
+// consecutive tiles from s * (T / S) + min(s, T % S). The kernel, the
+// launchers and the tests all call this one function.
+struct SplitKRange {
+  long first, count;
+};
+__host__ __device__ inline SplitKRange gemm_splitk_ktiles(long T, int S,
+                                                          int s) {
+  const long q = T / S, r = T % S;
+  return {s * q + (s < r ? s : r), q + (s < r ? 1 : 0)};
+}
+// The automatic split count (pure host; n_cu is the device's CU count).
+// M, N are rounded up to 128 and K to 64; tiles = (M/128)*(N/128),
+// T = K/64. 1 when tiles >= n_cu, else n_cu / tiles clamped to
+// [1, min(T / kSplitKMinTiles, kSplitKMaxSplits)]. Both constants come from
+// the sweep in profiles/gemm_splitk.md (scripts/gemm_splitk_sweep.py).
+constexpr int kSplitKMinTiles = 8;
+constexpr int kSplitKMaxSplits = 64;
+int gemm_splitk_plan(long M, long N, long K, int n_cu);
+// Workgroups of the fold kernel above which it walks grid-stride.
+constexpr int kSplitKReduceMaxGrid = 1024;
+// Throw std::runtime_error unless M,N % 128 == 0, K % 64 == 0,
+// 1 <= splits <= K / 64 and (splits == 1 or workspace != nullptr).
+void launch_gemm_splitk_bf16_nt(float* C, const void* A, const void* B,
+                                long M, long N, long K, int splits,
+                                void* workspace, hipStream_t stream,
+                                int xcd_swizzle = 0);
+void launch_gemm_splitk_fp8_nt(float* C, const void* A, const void* B,
+                               long M, long N, long K, int splits,
+                               void* workspace, hipStream_t stream,
+                               int xcd_swizzle = 0);
+void launch_gemm_splitk_i8_nt(int* C, const void* A, const void* B, long M,
+                              long N, long K, int splits, void* workspace,
+                              hipStream_t stream, int xcd_swizzle = 0);
+
 // MX quantize (quant.hip): the convert-to-MX step that makes the two MX
 // GEMMs' operands from real data. x is [rows][K] contiguous fp32 (or bf16
 // when x_is_bf16), K % 32 == 0; every 32 consecutive elements along K get

@@ -9,6 +9,8 @@ fallback.
 
 from __future__ import annotations
 
+import functools
+
 import torch
 
 from .._native import native
@@ -292,6 +294,95 @@ def gemm_i8(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
                         m, n, k, _stream_handle(stream), int(xcd_swizzle))
 
 
+# operand dtype -> (native kind, dtype of C and of the workspace)
+_SPLITK_KINDS = {torch.bfloat16: ("bf16", torch.float32),
+                 torch.float8_e4m3fn: ("fp8", torch.float32),
+                 torch.int8: ("i8", torch.int32)}
+
+
+def gemm_splitk(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                splits: int, workspace: torch.Tensor = None, stream=None,
+                xcd_swizzle: bool = False) -> None:
+    """K7 split-K: C[M,N] = A[M,K] @ B[N,K]^T with the K loop cut into
+    `splits` parts that run as separate workgroups (native/gemm_splitk.hip)
+    — for small M, N and a long K, where one workgroup per output tile
+    leaves most of the machine idle.
+
+    Dispatches on a.dtype: bf16 or float8_e4m3fn (c fp32), int8 (c int32,
+    exact). Split s of S walks T/S + (s < T%S) consecutive K-tiles of 64
+    (T = K/64) and writes its partial to workspace[s]; a second kernel on
+    the same stream computes C = ((P0 + P1) + P2) + ... in ascending s, so
+    the result is deterministic. splits == 1 writes C directly. Requires
+    M,N % 128 == 0, K % 64 == 0 and 1 <= splits <= K/64 (matmul_nt pads).
+
+    workspace: None allocates [splits, M, N] of c's dtype; a caller's must
+    be a contiguous CUDA tensor of c's dtype with at least splits*M*N
+    elements, starting on a 16-byte boundary. It is scratch: its first
+    splits*M*N elements are overwritten, the rest is not touched.
+    """
+    if a.dtype not in _SPLITK_KINDS:
+        raise TypeError(f"unsupported operand dtype {a.dtype}: gemm_splitk "
+                        f"takes bfloat16, float8_e4m3fn or int8")
+    kind, out_dtype = _SPLITK_KINDS[a.dtype]
+    if b.dtype != a.dtype or c.dtype != out_dtype:
+        raise TypeError(f"b must be {a.dtype} like a, and c {out_dtype}")
+    for t, name in ((c, "c"), (a, "a"), (b, "b")):
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise TypeError(f"{name} must be a contiguous 2-D CUDA tensor")
+    m, k = a.shape
+    n, kb = b.shape
+    if kb != k or c.shape != (m, n):
+        raise ValueError(f"shape mismatch: A{tuple(a.shape)} B{tuple(b.shape)}"
+                         f" C{tuple(c.shape)}")
+    if m < 128 or n < 128 or k < 64 or m % 128 or n % 128 or k % 64:
+        raise ValueError(f"gemm_splitk requires M,N % 128 == 0 and "
+                         f"K % 64 == 0; got M={m} N={n} K={k}")
+    splits = int(splits)
+    if not 1 <= splits <= k // 64:
+        raise ValueError(f"need 1 <= splits <= K/64 = {k // 64}; got {splits}")
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda \
+                or not workspace.is_contiguous() \
+                or workspace.dtype != c.dtype:
+            raise TypeError(f"workspace must be a contiguous {c.dtype} CUDA "
+                            f"tensor")
+        if workspace.numel() < splits * m * n:
+            raise ValueError(f"workspace holds {workspace.numel()} elements; "
+                             f"{splits} x {m} x {n} are needed")
+        if workspace.data_ptr() % 16 != 0:
+            raise ValueError("workspace must start on a 16-byte boundary")
+    ws_ptr = 0
+    if splits > 1:
+        if c.data_ptr() % 16 != 0:
+            raise ValueError("c must start on a 16-byte boundary")
+        if workspace is None:
+            workspace = torch.empty(splits, m, n, dtype=c.dtype,
+                                    device=c.device)
+            if hasattr(stream, "cuda_stream"):
+                # allocated on the current stream, used on another
+                workspace.record_stream(stream)
+        ws_ptr = workspace.data_ptr()
+    getattr(native(), f"gemm_splitk_{kind}_nt")(
+        c.data_ptr(), a.data_ptr(), b.data_ptr(), m, n, k, splits, ws_ptr,
+        _stream_handle(stream), int(xcd_swizzle))
+
+
+@functools.lru_cache(maxsize=None)
+def _device_cu_count(index: int) -> int:
+    return torch.cuda.get_device_properties(index).multi_processor_count
+
+
+def gemm_splitk_plan(m: int, n: int, k: int, n_cu: int = None) -> int:
+    """The split count matmul_nt(split_k="auto") uses for an (m, n, k)
+    problem: 1 when the 128^2 tiles already fill the n_cu compute units,
+    else n_cu // tiles, bounded so that every split keeps enough K-tiles
+    (constants and the sweep behind them: docs/gemm.md, "Split-K").
+    n_cu=None reads the current device. Pure shape math otherwise."""
+    if n_cu is None:
+        n_cu = _device_cu_count(torch.cuda.current_device())
+    return native().gemm_splitk_plan(int(m), int(n), int(k), int(n_cu))
+
+
 def gemm_pad_shapes(kind: str, m: int, n: int, k: int):
     """Padded (M, N, K) that puts a (m, n, k) problem on the fast path.
 
@@ -321,7 +412,8 @@ def _pad2d(t: torch.Tensor, rows: int, cols: int, fill=0):
 
 def matmul_nt(a: torch.Tensor, b: torch.Tensor,
               a_scale: torch.Tensor = None, b_scale: torch.Tensor = None,
-              stream=None, xcd_swizzle: bool = False) -> torch.Tensor:
+              stream=None, xcd_swizzle: bool = False,
+              split_k=None) -> torch.Tensor:
     """Arbitrary-shape front door to the K7 GEMM family: returns A @ B^T.
 
     Dispatches on dtype — bf16 -> gemm_bf16, float8_e4m3fn -> gemm_fp8
@@ -333,12 +425,45 @@ def matmul_nt(a: torch.Tensor, b: torch.Tensor,
     region of C is sliced away (result is a fresh contiguous tensor when
     padding occurred). Scale padding uses 127 (= 2^0) — irrelevant since
     the padded data is zero.
+
+    split_k (bf16, fp8 and int8 without scales only): None keeps the path
+    above. An int runs gemm_splitk with that many splits, after padding M
+    and N to 128 and K to 64 only. "auto" asks gemm_splitk_plan: small M, N
+    with a long K take the split path, everything the plan answers 1 for
+    keeps the path above and its 256^2 kernels.
     """
     if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
         raise ValueError(f"need A[M,K], B[N,K]; got A{tuple(a.shape)} "
                          f"B{tuple(b.shape)}")
     m, k = a.shape
     n = b.shape[0]
+    if split_k is not None:
+        if a_scale is not None or b_scale is not None \
+                or a.dtype == torch.uint8:
+            raise ValueError("split_k does not take MX operands (scales or "
+                             "packed fp4): the scale rows need a staging of "
+                             "their own")
+        if a.dtype not in _SPLITK_KINDS:
+            raise TypeError(f"unsupported operand dtype {a.dtype}")
+        if split_k == "auto":
+            splits = gemm_splitk_plan(m, n, k)
+        elif isinstance(split_k, int) and not isinstance(split_k, bool):
+            splits = split_k
+        else:
+            raise ValueError(f"split_k must be None, an int or 'auto'; got "
+                             f"{split_k!r}")
+        if split_k != "auto" or splits > 1:
+            mp, np_, kp = -(-m // 128) * 128, -(-n // 128) * 128, \
+                -(-k // 64) * 64
+            ap = _pad2d(a.contiguous(), mp, kp)
+            bp = _pad2d(b.contiguous(), np_, kp)
+            c = torch.empty(mp, np_, dtype=_SPLITK_KINDS[a.dtype][1],
+                            device=a.device)
+            gemm_splitk(c, ap, bp, splits, stream=stream,
+                        xcd_swizzle=xcd_swizzle)
+            if (mp, np_) == (m, n):
+                return c
+            return c[:m, :n].contiguous()
     if a.dtype == torch.bfloat16:
         kind, fn, out_dtype = "bf16", gemm_bf16, torch.float32
     elif a.dtype == torch.int8:
