@@ -152,6 +152,20 @@ void launch_gemm_splitk_i8_nt(int* C, const void* A, const void* B, long M,
                               long N, long K, int splits, void* workspace,
                               hipStream_t stream, int xcd_swizzle = 0);
 
+// Operand layouts (gemm_layout.hip): the bf16 128^2-tile GEMM for operands
+// that are not K-contiguous. `layout` names transA then transB, row-major:
+//   "nn": A [M,K], B [K,N]    "tn": A [K,M], B [K,N]    "tt": A [K,M], B [N,K]
+// C [M,N] fp32. An operand stored [K, X] is staged by the same 16-byte
+// DMAs and read from LDS with ds_read_b64_tr_b16; the result is the bits
+// bf16_db8 gives on a materialised transpose. Contract: docs/gemm.md.
+// Throws std::runtime_error unless M,N % 128 == 0, K % 64 == 0 and A, B
+// start on 16-byte boundaries; std::invalid_argument on any other layout
+// string, "nt" included (launch_gemm_bf16_nt owns it). Tile order:
+// row-major unless HPK_GEMM_GROUP is set.
+void launch_gemm_bf16_layout(float* C, const void* A, const void* B, long M,
+                             long N, long K, const char* layout,
+                             hipStream_t stream, int xcd_swizzle = 0);
+
 // MX quantize (quant.hip): the convert-to-MX step that makes the two MX
 // GEMMs' operands from real data. x is [rows][K] contiguous fp32 (or bf16
 // when x_is_bf16), K % 32 == 0; every 32 consecutive elements along K get

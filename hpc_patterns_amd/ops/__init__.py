@@ -663,3 +663,191 @@ def matmul_mx(a: torch.Tensor, b: torch.Tensor, fmt: str = "mxfp8",
     aq, a_scale = quantize_mx(operand(a), fmt, stream=stream)
     bq, b_scale = quantize_mx(operand(b), fmt, stream=stream)
     return matmul_nt(aq, bq, a_scale, b_scale, stream=stream)
+
+
+# ---------------------------------------------------------------------------
+# Operand layouts: bf16 products whose operands are not K-contiguous
+# (native/gemm_layout.hip). Contract: docs/gemm.md, "Operand layouts".
+# ---------------------------------------------------------------------------
+
+# layout -> (A is stored [K,M], B is stored [K,N]); row-major names, transA
+# then transB. "nt" is the rest of the family.
+_LAYOUTS = {"nn": (False, True), "tn": (True, True), "tt": (True, False)}
+
+_NO_NARROW_TR = ("only bf16 has the nn/tn/tt layouts: the 8-bit and 4-bit "
+                 "transposed LDS reads (ds_read_b64_tr_b8 / _tr_b4) are not "
+                 "built here; pass K-contiguous operands (layout nt)")
+
+
+def gemm_bf16_layout(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                     layout: str, stream=None,
+                     xcd_swizzle: bool = False) -> None:
+    """K7 layouts: C[M,N] fp32 = op(A) @ op(B) on bf16 operands AS STORED.
+
+        layout  a        b
+        "nn"    [M,K]    [K,N]
+        "tn"    [K,M]    [K,N]
+        "tt"    [K,M]    [N,K]
+        "nt"    [M,K]    [N,K]   (forwards to gemm_bf16)
+
+    An operand stored [K, X] is staged by the family's 16-byte DMAs along
+    its contiguous dimension and transposed on the way out of LDS by
+    ds_read_b64_tr_b16 — no transposed copy in HBM. The result is bit for
+    bit what gemm_bf16's double-buffered 128^2 kernel (HPK_GEMM_VARIANT=db)
+    gives on t().contiguous() copies. Requires M,N % 128 == 0, K % 64 == 0
+    and a, b starting on 16-byte boundaries (matmul pads). Any other layout
+    string raises ValueError.
+    """
+    if layout == "nt":
+        return gemm_bf16(c, a, b, stream=stream, xcd_swizzle=xcd_swizzle)
+    if layout not in _LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}; expected one of "
+                         f"'nn', 'tn', 'tt', 'nt'")
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+        if a.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8):
+            raise TypeError(_NO_NARROW_TR)
+        raise TypeError("c must be fp32; a, b must be bf16")
+    if c.dtype != torch.float32:
+        raise TypeError("c must be fp32; a, b must be bf16")
+    for t, name in ((c, "c"), (a, "a"), (b, "b")):
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise TypeError(f"{name} must be a contiguous 2-D CUDA tensor")
+    a_t, b_n = _LAYOUTS[layout]
+    k, m = a.shape if a_t else a.shape[::-1]
+    kb, n = b.shape if b_n else b.shape[::-1]
+    if kb != k or c.shape != (m, n):
+        raise ValueError(f"shape mismatch for layout {layout}: "
+                         f"A{tuple(a.shape)} B{tuple(b.shape)} "
+                         f"C{tuple(c.shape)}")
+    if m < 128 or n < 128 or k < 64 or m % 128 or n % 128 or k % 64:
+        raise ValueError(f"gemm_bf16_layout requires M,N % 128 == 0 and "
+                         f"K % 64 == 0; got M={m} N={n} K={k}")
+    if a.data_ptr() % 16 != 0 or b.data_ptr() % 16 != 0:
+        raise ValueError("a and b must start on 16-byte boundaries (they "
+                         "are fetched in 16-byte chunks)")
+    native().gemm_bf16_layout(c.data_ptr(), a.data_ptr(), b.data_ptr(),
+                              m, n, k, layout, _stream_handle(stream),
+                              int(xcd_swizzle))
+
+
+def matmul_layout(a: torch.Tensor, b: torch.Tensor):
+    """(layout, a_stored, b_stored) of the logical product a [M,K] @ b [K,N],
+    read from the strides; pure tensor metadata, any device.
+
+    Each argument is row-major contiguous or the .t() view of a row-major
+    contiguous tensor; a_stored / b_stored are those contiguous tensors
+    (views, never copies). a row-major is "n", its .t() view "t"; b
+    row-major [K,N] is "n", the .t() view of a stored [N,K] is "t".
+    is_contiguous() is asked first, so a tensor with a size-1 dimension —
+    whose strides fit both readings, the memory being the same — counts as
+    row-major. Anything else raises TypeError.
+    """
+    def stored(t, name):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f"{name} must be a 2-D tensor")
+        if t.is_contiguous():
+            return t, "n"
+        if t.t().is_contiguous():
+            return t.t(), "t"
+        raise TypeError(f"{name} is neither row-major contiguous nor the "
+                        f".t() view of such a tensor (shape "
+                        f"{tuple(t.shape)}, strides {t.stride()}); "
+                        f"matmul makes no hidden copies")
+    a_st, fa = stored(a, "a")
+    b_st, fb = stored(b, "b")
+    if a.shape[1] != b.shape[0]:
+        raise ValueError(f"need a[M,K] @ b[K,N]; got a{tuple(a.shape)} "
+                         f"b{tuple(b.shape)}")
+    return fa + fb, a_st, b_st
+
+
+def gemm_layout_pad_shapes(m: int, n: int, k: int):
+    """Padded (M, N, K) of the nn/tn/tt kernels: M, N up to 128, K to 64."""
+    return -(-m // 128) * 128, -(-n // 128) * 128, -(-k // 64) * 64
+
+
+def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
+           xcd_swizzle: bool = False) -> torch.Tensor:
+    """Layout-agnostic front door: returns the logical a [M,K] @ b [K,N].
+
+    The layout is read from the strides (matmul_layout: row-major or a
+    .t() view; no hidden .contiguous() copies, anything else is a
+    TypeError). nt — b the .t() view of a stored [N,K] — goes to matmul_nt
+    in every dtype it takes without scales. nn, tn and tt are bf16 only:
+    the stored tensors are zero-padded to multiples of 128 / 128 / 64
+    (zeros add nothing, so the result is the unpadded product bit for bit)
+    and run through gemm_bf16_layout; other dtypes raise TypeError. A stored
+    tensor that needs no padding but starts off a 16-byte boundary is
+    cloned. This change does not switch kernels on size: at large shapes a
+    t().contiguous() copy plus the 256^2 kernel of matmul_nt can be faster
+    (docs/gemm.md, "Operand layouts").
+    """
+    layout, a_st, b_st = matmul_layout(a, b)
+    if a.dtype != b.dtype:
+        raise TypeError(f"a is {a.dtype}, b is {b.dtype}")
+    if layout == "nt":
+        return matmul_nt(a_st, b_st, stream=stream, xcd_swizzle=xcd_swizzle)
+    if a.dtype != torch.bfloat16:
+        if a.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8):
+            raise TypeError(_NO_NARROW_TR)
+        raise TypeError(f"unsupported operand dtype {a.dtype}")
+    m, k = a.shape
+    n = b.shape[1]
+    mp, np_, kp = gemm_layout_pad_shapes(m, n, k)
+    a_t, b_n = _LAYOUTS[layout]
+
+    def operand(t, rows, cols):
+        t = _pad2d(t, rows, cols)
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+
+    ap = operand(a_st, *((kp, mp) if a_t else (mp, kp)))
+    bp = operand(b_st, *((kp, np_) if b_n else (np_, kp)))
+    c = torch.empty(mp, np_, dtype=torch.float32, device=a.device)
+    gemm_bf16_layout(c, ap, bp, layout, stream=stream,
+                     xcd_swizzle=xcd_swizzle)
+    if (mp, np_) == (m, n):
+        return c
+    return c[:m, :n].contiguous()
+
+
+class _LinearBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x, w)
+        return matmul_nt(x, w).to(torch.bfloat16)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        if not dy.is_contiguous():  # e.g. the expanded scalar of sum()
+            dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = matmul(dy, w).to(torch.bfloat16)       # nn: dy [M,N] w [N,K]
+        if ctx.needs_input_grad[1]:
+            dw = matmul(dy.t(), x).to(torch.bfloat16)   # tn: dy [M,N] x [M,K]
+        return dx, dw
+
+
+def linear_bf16(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """y = x @ w^T for bf16 x [M,K] and w [N,K], differentiable; every
+    product runs on the K7 kernels with fp32 accumulation and is cast to
+    bf16, and nothing is transposed in memory:
+
+        forward   y  = matmul_nt(x, w)       nt
+        backward  dx = matmul(dy, w)         nn
+                  dw = matmul(dy.t(), x)     tn
+
+    dw sums over the token dimension M. With many tokens and a small
+    weight that is a split-K shape (few output tiles, a long sum); the
+    layout kernel has no split-K member yet, so such a dw runs on
+    (N/128)*(K/128) workgroups.
+    """
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"need x[M,K], w[N,K]; got x{tuple(x.shape)} "
+                         f"w{tuple(w.shape)}")
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise TypeError("x and w must be bf16")
+    if not x.is_contiguous() or not w.is_contiguous():
+        raise TypeError("x and w must be contiguous")
+    return _LinearBf16.apply(x, w)
