@@ -176,6 +176,11 @@ def gemm_mxfp8(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
     with ONE scale per 32-element K-block ([M,K//32] / [N,K//32]; 127 =
     scale 1.0) — the OCP MX-FP8 format, dequantized in hardware by
     mfma_scale_f32_16x16x128_f8f6f4. Requires M,N,K multiples of 128.
+
+    Scale bytes 0..254 are all exact (the exponents of both scales add;
+    only the product has to fit fp32). Byte 255 is the e8m0 NaN: the
+    block reads as all NaN, like the element codes 0x7F / 0xFF, and makes
+    its row / column of C NaN (findings.md #31).
     """
     if c.dtype != torch.float32 or a.dtype != torch.float8_e4m3fn \
             or b.dtype != torch.float8_e4m3fn:
@@ -249,6 +254,10 @@ def gemm_mxfp4(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
     (3.2 PFLOP/s; HPK_MX4_WAVES=db|8|4 selects the 128^2 variants, used
     automatically when M or N is not a multiple of 256). K =
     2*a.shape[1]; requires M,N,K % 128 == 0.
+
+    Scale bytes 0..254 are all exact, as for gemm_mxfp8. e2m1 has no NaN
+    code, but scale byte 255 (e8m0 NaN) makes its block all NaN and so
+    its row / column of C (findings.md #31).
     """
     if c.dtype != torch.float32 or a.dtype != torch.uint8 \
             or b.dtype != torch.uint8:
@@ -613,7 +622,9 @@ def quantize_mx(x: torch.Tensor, fmt: str, stream=None):
     +-448 / +-6 and rounded to nearest-even. "mxfp8": q is float8_e4m3fn
     [rows, K]; "mxfp4": q is uint8 [rows, K//2], low nibble = even k (the
     e2m1_pack layout). scale is uint8 [rows, K//32]. Full contract:
-    docs/gemm.md. K must be a multiple of 32 (matmul_mx pads).
+    docs/gemm.md. K must be a multiple of 32 (matmul_mx pads). The element
+    codes of a scale-255 block are unspecified; the MX GEMMs read such a
+    block as all NaN whatever they are (findings.md #31).
     """
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise TypeError("x must be a CUDA tensor")
@@ -648,6 +659,10 @@ def matmul_mx(a: torch.Tensor, b: torch.Tensor, fmt: str = "mxfp8",
     K is zero-padded up to a multiple of 32 (zeros change no block
     maximum), both operands go through quantize_mx, and matmul_nt does
     the tile padding and picks the kernel.
+
+    An Inf or NaN in a makes row i of the result NaN, one in b column j
+    (its block gets scale byte 255, which the scaled MFMAs read as NaN);
+    every other output is unaffected (tests/test_gpu_gemm_specials.py).
     """
     _mx_format(fmt)
     if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:

@@ -167,9 +167,9 @@ def _full_range_operand(kind, rows, k, g):
         # random finite bit patterns, exponent field 2..253: every product
         # with a weight in {+-1, 2, 0.5} then stays a normal, finite fp32
         # (field 254 times 2 overflows, which the float64 reference does
-        # not survive; field 1 times 0.5 is an fp32 subnormal). bf16
-        # SUBNORMAL inputs (field 0) are left out on purpose: whether the
-        # bf16 MFMA flushes them is unmeasured in this project.
+        # not survive; field 1 times 0.5 is an fp32 subnormal). Those ends,
+        # bf16 SUBNORMAL inputs (field 0) and NaN/Inf have a reference and
+        # a comparison rule of their own: tests/test_gpu_gemm_specials.py.
         sign = torch.randint(0, 2, (n,), generator=g)
         exp = torch.randint(2, 254, (n,), generator=g)
         man = torch.randint(0, 128, (n,), generator=g)
