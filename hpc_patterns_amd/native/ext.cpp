@@ -185,6 +185,22 @@ PYBIND11_MODULE(_hpk, m) {
         py::arg("xcd_swizzle") = 0,
         "layout: nn (A [M,K], B [K,N]), tn (A [K,M], B [K,N]) or tt "
         "(A [K,M], B [N,K])");
+  m.def("gemm_bf16_layout_splitk",
+        [](uintptr_t c, uintptr_t a, uintptr_t b, long m, long n, long k,
+           const std::string& layout, int splits, uintptr_t workspace,
+           uintptr_t stream, int xcd_swizzle) {
+          hpk::launch_gemm_bf16_layout_splitk(
+              reinterpret_cast<float*>(c), reinterpret_cast<const void*>(a),
+              reinterpret_cast<const void*>(b), m, n, k, layout.c_str(),
+              splits, reinterpret_cast<void*>(workspace), as_stream(stream),
+              xcd_swizzle);
+        },
+        py::arg("c"), py::arg("a"), py::arg("b"), py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("layout"), py::arg("splits"),
+        py::arg("workspace") = 0, py::arg("stream") = 0,
+        py::arg("xcd_swizzle") = 0,
+        "split-K over the nn / tn / tt layouts of gemm_bf16_layout; "
+        "workspace [splits][M][N] fp32 when splits > 1");
   m.attr("SPLITK_MIN_TILES") = hpk::kSplitKMinTiles;
   m.attr("SPLITK_MAX_SPLITS") = hpk::kSplitKMaxSplits;
   m.attr("SPLITK_REDUCE_MAX_GRID") = hpk::kSplitKReduceMaxGrid;

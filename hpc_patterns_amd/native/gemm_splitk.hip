@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 namespace hpk {
 namespace {
@@ -213,6 +214,18 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(
   }
 }
 
+// the fold's one launch site: nvec / 256 workgroups, grid-stride above
+// kSplitKReduceMaxGrid
+template <class V>
+void launch_reduce(const char* label, void* C, const void* workspace,
+                   long nvec, int S, hipStream_t stream) {
+  long grid = nvec / 256;
+  if (grid > kSplitKReduceMaxGrid) grid = kSplitKReduceMaxGrid;
+  hipLaunchKernelGGL(k_splitk_reduce<V>, dim3((unsigned)grid), dim3(256), 0,
+                     stream, (V*)C, (const V*)workspace, nvec, S);
+  check_hip(hipGetLastError(), label);
+}
+
 template <class Tr, class V>
 void launch_splitk(const char* kind, typename Tr::Out* C, const void* A,
                    const void* B, long M, long N, long K, int splits,
@@ -245,11 +258,11 @@ void launch_splitk(const char* kind, typename Tr::Out* C, const void* A,
   check_hip(hipGetLastError(), ("launch_" + what).c_str());
   if (splits == 1) return;
   const long nvec = M * N / 4;
-  long grid = nvec / 256;
-  if (grid > kSplitKReduceMaxGrid) grid = kSplitKReduceMaxGrid;
-  hipLaunchKernelGGL(k_splitk_reduce<V>, dim3((unsigned)grid), dim3(256), 0,
-                     stream, (V*)C, (const V*)workspace, nvec, splits);
-  check_hip(hipGetLastError(), ("launch_" + what + "(reduce)").c_str());
+  if constexpr (std::is_same<V, f32x4>::value)
+    launch_splitk_reduce_f32(C, workspace, nvec, splits, stream);
+  else
+    launch_reduce<V>(("launch_" + what + "(reduce)").c_str(), C, workspace,
+                     nvec, splits, stream);
 }
 
 } // namespace
@@ -272,6 +285,22 @@ void launch_gemm_splitk_bf16_nt(float* C, const void* A, const void* B,
                                 int xcd_swizzle) {
   launch_splitk<SkBf16, f32x4>("bf16", C, A, B, M, N, K, splits, workspace,
                                stream, xcd_swizzle);
+}
+
+// Stands here, behind the first use of the bf16 tile kernel, so that the
+// kernels keep the order in the code object they had before the fold
+// became a function of its own.
+void launch_splitk_reduce_f32(float* C, const void* workspace, long nvec,
+                              int S, hipStream_t stream) {
+  if (C == nullptr || workspace == nullptr || nvec < 256 || nvec % 256 != 0 ||
+      S < 2)
+    throw std::runtime_error("splitk_reduce_f32 requires C, a workspace, "
+                             "nvec % 256 == 0 and S >= 2");
+  if ((uintptr_t)C % 16 != 0 || (uintptr_t)workspace % 16 != 0)
+    throw std::runtime_error("splitk_reduce_f32 requires C and the workspace "
+                             "on 16-byte boundaries");
+  launch_reduce<f32x4>("launch_splitk_reduce_f32", C, workspace, nvec, S,
+                       stream);
 }
 
 void launch_gemm_splitk_fp8_nt(float* C, const void* A, const void* B,

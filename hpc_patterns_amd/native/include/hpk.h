@@ -138,6 +138,14 @@ constexpr int kSplitKMaxSplits = 64;
 int gemm_splitk_plan(long M, long N, long K, int n_cu);
 // Workgroups of the fold kernel above which it walks grid-stride.
 constexpr int kSplitKReduceMaxGrid = 1024;
+// The fold alone, for fp32 partials: C[i] = ((P0[i] + P1[i]) + ...) over the
+// S slices of `workspace` ([S][nvec] 16-byte vectors, nvec = M * N / 4), on
+// `stream`, behind whatever wrote the slices there. The split-K launchers
+// below and launch_gemm_bf16_layout_splitk share it. Throws
+// std::runtime_error unless nvec % 256 == 0, S >= 2 and both pointers are
+// non-null and on 16-byte boundaries.
+void launch_splitk_reduce_f32(float* C, const void* workspace, long nvec,
+                              int S, hipStream_t stream);
 // Throw std::runtime_error unless M,N % 128 == 0, K % 64 == 0,
 // 1 <= splits <= K / 64 and (splits == 1 or workspace != nullptr).
 void launch_gemm_splitk_bf16_nt(float* C, const void* A, const void* B,
@@ -165,6 +173,24 @@ void launch_gemm_splitk_i8_nt(int* C, const void* A, const void* B, long M,
 void launch_gemm_bf16_layout(float* C, const void* A, const void* B, long M,
                              long N, long K, const char* layout,
                              hipStream_t stream, int xcd_swizzle = 0);
+// Split-K for the same three layouts (gemm_layout_splitk.hip), for the dW
+// product of a linear layer: a small [M,N] output summed over a long K (the
+// tokens). Grid (tiles, splits); split s walks the K-tiles
+// gemm_splitk_ktiles(K / 64, splits, s) — for an operand stored [K, X]
+// those are ROWS kbeg .. of the tensor — and writes its partial to slice s
+// of `workspace` ([splits][M][N] fp32); launch_splitk_reduce_f32 folds the
+// slices in ascending s. splits == 1 writes C directly: no workspace, no
+// second kernel, and the bits of launch_gemm_bf16_layout. For every splits
+// the result is the bits of launch_gemm_splitk_bf16_nt on materialised
+// transposes. Throws as launch_gemm_bf16_layout does, and
+// std::runtime_error unless 1 <= splits <= min(K / 64, 65535) and, when
+// splits > 1, workspace is non-null and C and workspace are on 16-byte
+// boundaries.
+void launch_gemm_bf16_layout_splitk(float* C, const void* A, const void* B,
+                                    long M, long N, long K,
+                                    const char* layout, int splits,
+                                    void* workspace, hipStream_t stream,
+                                    int xcd_swizzle = 0);
 
 // MX quantize (quant.hip): the convert-to-MX step that makes the two MX
 // GEMMs' operands from real data. x is [rows][K] contiguous fp32 (or bf16

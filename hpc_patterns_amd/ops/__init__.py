@@ -745,6 +745,89 @@ def gemm_bf16_layout(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
                               int(xcd_swizzle))
 
 
+def gemm_bf16_layout_splitk(c: torch.Tensor, a: torch.Tensor,
+                            b: torch.Tensor, layout: str, splits: int,
+                            workspace: torch.Tensor = None, stream=None,
+                            xcd_swizzle: bool = False) -> None:
+    """K7 layouts, split-K: gemm_bf16_layout with the K loop cut into
+    `splits` parts that run as separate workgroups
+    (native/gemm_layout_splitk.hip) — for the dW product of a linear layer,
+    dW[N,K] = dy[M,N]^T @ x[M,K] (layout "tn" on the tensors as stored),
+    whose output is a weight and whose sum runs over the tokens.
+
+    Operands, layouts and their rules are gemm_bf16_layout's; splits,
+    workspace and the fold are gemm_splitk's: split s of S walks
+    T/S + (s < T%S) consecutive K-tiles of 64 (T = K/64) — rows of an
+    operand stored [K, X] — and writes its partial to workspace[s]; a
+    second kernel on the same stream computes C = ((P0 + P1) + P2) + ... in
+    ascending s. splits == 1 writes C directly and gives gemm_bf16_layout's
+    bits; every splits gives the bits of gemm_splitk on t().contiguous()
+    copies. Requires M,N % 128 == 0, K % 64 == 0, 1 <= splits <= K/64
+    (matmul pads). layout "nt" forwards to gemm_splitk.
+
+    workspace: None allocates [splits, M, N] fp32; a caller's must be a
+    contiguous fp32 CUDA tensor with at least splits*M*N elements, starting
+    on a 16-byte boundary. It is scratch: its first splits*M*N elements are
+    overwritten, the rest is not touched.
+    """
+    if layout == "nt":
+        return gemm_splitk(c, a, b, splits, workspace=workspace,
+                           stream=stream, xcd_swizzle=xcd_swizzle)
+    if layout not in _LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}; expected one of "
+                         f"'nn', 'tn', 'tt', 'nt'")
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+        if a.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8):
+            raise TypeError(_NO_NARROW_TR)
+        raise TypeError("c must be fp32; a, b must be bf16")
+    if c.dtype != torch.float32:
+        raise TypeError("c must be fp32; a, b must be bf16")
+    for t, name in ((c, "c"), (a, "a"), (b, "b")):
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise TypeError(f"{name} must be a contiguous 2-D CUDA tensor")
+    a_t, b_n = _LAYOUTS[layout]
+    k, m = a.shape if a_t else a.shape[::-1]
+    kb, n = b.shape if b_n else b.shape[::-1]
+    if kb != k or c.shape != (m, n):
+        raise ValueError(f"shape mismatch for layout {layout}: "
+                         f"A{tuple(a.shape)} B{tuple(b.shape)} "
+                         f"C{tuple(c.shape)}")
+    if m < 128 or n < 128 or k < 64 or m % 128 or n % 128 or k % 64:
+        raise ValueError(f"gemm_bf16_layout_splitk requires M,N % 128 == 0 "
+                         f"and K % 64 == 0; got M={m} N={n} K={k}")
+    if a.data_ptr() % 16 != 0 or b.data_ptr() % 16 != 0:
+        raise ValueError("a and b must start on 16-byte boundaries (they "
+                         "are fetched in 16-byte chunks)")
+    splits = int(splits)
+    if not 1 <= splits <= k // 64:
+        raise ValueError(f"need 1 <= splits <= K/64 = {k // 64}; got {splits}")
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda \
+                or not workspace.is_contiguous() \
+                or workspace.dtype != c.dtype:
+            raise TypeError(f"workspace must be a contiguous {c.dtype} CUDA "
+                            f"tensor")
+        if workspace.numel() < splits * m * n:
+            raise ValueError(f"workspace holds {workspace.numel()} elements; "
+                             f"{splits} x {m} x {n} are needed")
+        if workspace.data_ptr() % 16 != 0:
+            raise ValueError("workspace must start on a 16-byte boundary")
+    ws_ptr = 0
+    if splits > 1:
+        if c.data_ptr() % 16 != 0:
+            raise ValueError("c must start on a 16-byte boundary")
+        if workspace is None:
+            workspace = torch.empty(splits, m, n, dtype=c.dtype,
+                                    device=c.device)
+            if hasattr(stream, "cuda_stream"):
+                # allocated on the current stream, used on another
+                workspace.record_stream(stream)
+        ws_ptr = workspace.data_ptr()
+    native().gemm_bf16_layout_splitk(
+        c.data_ptr(), a.data_ptr(), b.data_ptr(), m, n, k, layout, splits,
+        ws_ptr, _stream_handle(stream), int(xcd_swizzle))
+
+
 def matmul_layout(a: torch.Tensor, b: torch.Tensor):
     """(layout, a_stored, b_stored) of the logical product a [M,K] @ b [K,N],
     read from the strides; pure tensor metadata, any device.
@@ -781,8 +864,19 @@ def gemm_layout_pad_shapes(m: int, n: int, k: int):
     return -(-m // 128) * 128, -(-n // 128) * 128, -(-k // 64) * 64
 
 
+def _check_split_k(split_k, ints: bool):
+    """split_k of matmul (ints) / linear_bf16 (no ints), on its type and
+    value alone: before any tensor is looked at"""
+    if split_k is None or (isinstance(split_k, str) and split_k == "auto"):
+        return
+    if ints and isinstance(split_k, int) and not isinstance(split_k, bool):
+        return
+    raise ValueError(f"split_k must be None{', an int' if ints else ''} or "
+                     f"'auto'; got {split_k!r}")
+
+
 def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
-           xcd_swizzle: bool = False) -> torch.Tensor:
+           xcd_swizzle: bool = False, split_k=None) -> torch.Tensor:
     """Layout-agnostic front door: returns the logical a [M,K] @ b [K,N].
 
     The layout is read from the strides (matmul_layout: row-major or a
@@ -796,12 +890,22 @@ def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
     cloned. This change does not switch kernels on size: at large shapes a
     t().contiguous() copy plus the 256^2 kernel of matmul_nt can be faster
     (docs/gemm.md, "Operand layouts").
+
+    split_k: None keeps the path above. It is checked first — None, an int
+    or "auto", anything else is a ValueError — and nt hands it to matmul_nt.
+    For nn, tn and tt an int runs gemm_bf16_layout_splitk with that many
+    splits on the same padded tensors (1 <= split_k <= K_padded / 64, else
+    ValueError); "auto" asks gemm_splitk_plan(m, n, k): a small output with
+    a long sum — dW = dy^T x over many tokens — takes the split path,
+    everything the plan answers 1 for keeps the path above.
     """
+    _check_split_k(split_k, ints=True)
     layout, a_st, b_st = matmul_layout(a, b)
     if a.dtype != b.dtype:
         raise TypeError(f"a is {a.dtype}, b is {b.dtype}")
     if layout == "nt":
-        return matmul_nt(a_st, b_st, stream=stream, xcd_swizzle=xcd_swizzle)
+        return matmul_nt(a_st, b_st, stream=stream, xcd_swizzle=xcd_swizzle,
+                         split_k=split_k)
     if a.dtype != torch.bfloat16:
         if a.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8):
             raise TypeError(_NO_NARROW_TR)
@@ -810,6 +914,15 @@ def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
     n = b.shape[1]
     mp, np_, kp = gemm_layout_pad_shapes(m, n, k)
     a_t, b_n = _LAYOUTS[layout]
+    splits = None  # None: the kernel without a split
+    if split_k == "auto":
+        plan = gemm_splitk_plan(m, n, k)
+        splits = plan if plan > 1 else None
+    elif split_k is not None:
+        if not 1 <= split_k <= kp // 64:
+            raise ValueError(f"need 1 <= split_k <= K_padded/64 = {kp // 64} "
+                             f"(K = {k} padded to {kp}); got {split_k}")
+        splits = split_k
 
     def operand(t, rows, cols):
         t = _pad2d(t, rows, cols)
@@ -818,8 +931,12 @@ def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
     ap = operand(a_st, *((kp, mp) if a_t else (mp, kp)))
     bp = operand(b_st, *((kp, np_) if b_n else (np_, kp)))
     c = torch.empty(mp, np_, dtype=torch.float32, device=a.device)
-    gemm_bf16_layout(c, ap, bp, layout, stream=stream,
-                     xcd_swizzle=xcd_swizzle)
+    if splits is None:
+        gemm_bf16_layout(c, ap, bp, layout, stream=stream,
+                         xcd_swizzle=xcd_swizzle)
+    else:
+        gemm_bf16_layout_splitk(c, ap, bp, layout, splits, stream=stream,
+                                xcd_swizzle=xcd_swizzle)
     if (mp, np_) == (m, n):
         return c
     return c[:m, :n].contiguous()
@@ -827,24 +944,27 @@ def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
 
 class _LinearBf16(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w):
+    def forward(ctx, x, w, split_k):
         ctx.save_for_backward(x, w)
-        return matmul_nt(x, w).to(torch.bfloat16)
+        ctx.split_k = split_k
+        return matmul_nt(x, w, split_k=split_k).to(torch.bfloat16)
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
+        sk = ctx.split_k
         if not dy.is_contiguous():  # e.g. the expanded scalar of sum()
             dy = dy.contiguous()
         dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = matmul(dy, w).to(torch.bfloat16)       # nn: dy [M,N] w [N,K]
-        if ctx.needs_input_grad[1]:
-            dw = matmul(dy.t(), x).to(torch.bfloat16)   # tn: dy [M,N] x [M,K]
-        return dx, dw
+        if ctx.needs_input_grad[0]:     # nn: dy [M,N] w [N,K]
+            dx = matmul(dy, w, split_k=sk).to(torch.bfloat16)
+        if ctx.needs_input_grad[1]:     # tn: dy [M,N] x [M,K]
+            dw = matmul(dy.t(), x, split_k=sk).to(torch.bfloat16)
+        return dx, dw, None
 
 
-def linear_bf16(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+def linear_bf16(x: torch.Tensor, w: torch.Tensor,
+                split_k=None) -> torch.Tensor:
     """y = x @ w^T for bf16 x [M,K] and w [N,K], differentiable; every
     product runs on the K7 kernels with fp32 accumulation and is cast to
     bf16, and nothing is transposed in memory:
@@ -854,10 +974,16 @@ def linear_bf16(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
                   dw = matmul(dy.t(), x)     tn
 
     dw sums over the token dimension M. With many tokens and a small
-    weight that is a split-K shape (few output tiles, a long sum); the
-    layout kernel has no split-K member yet, so such a dw runs on
-    (N/128)*(K/128) workgroups.
+    weight that is a split-K shape (few output tiles, a long sum), and
+    without a split it runs on (N/128)*(K/128) workgroups. split_k="auto"
+    hands "auto" to all three products, so each one gemm_splitk_plan
+    answers more than 1 for — in practice such a dw — runs split over the
+    machine (gemm_bf16_layout_splitk); its fp32 summation order, and with
+    it possibly the last bit of the result, then differs from the default's.
+    split_k is None (the default: no split anywhere) or "auto"; anything
+    else is a ValueError.
     """
+    _check_split_k(split_k, ints=False)
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
         raise ValueError(f"need x[M,K], w[N,K]; got x{tuple(x.shape)} "
                          f"w{tuple(w.shape)}")
@@ -865,4 +991,4 @@ def linear_bf16(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         raise TypeError("x and w must be bf16")
     if not x.is_contiguous() or not w.is_contiguous():
         raise TypeError("x and w must be contiguous")
-    return _LinearBf16.apply(x, w)
+    return _LinearBf16.apply(x, w, split_k)
