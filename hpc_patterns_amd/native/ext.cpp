@@ -201,6 +201,65 @@ PYBIND11_MODULE(_hpk, m) {
         py::arg("xcd_swizzle") = 0,
         "split-K over the nn / tn / tt layouts of gemm_bf16_layout; "
         "workspace [splits][M][N] fp32 when splits > 1");
+  m.def("gemm_bf16_epilogue",
+        [](uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t bias, long m,
+           long n, long k, const std::string& layout, int splits,
+           uintptr_t workspace, uintptr_t stream, int xcd_swizzle) {
+          hpk::launch_gemm_bf16_epilogue(
+              reinterpret_cast<void*>(c), reinterpret_cast<const void*>(a),
+              reinterpret_cast<const void*>(b),
+              reinterpret_cast<const float*>(bias), m, n, k, layout.c_str(),
+              splits, reinterpret_cast<void*>(workspace), as_stream(stream),
+              xcd_swizzle);
+        },
+        py::arg("c"), py::arg("a"), py::arg("b"), py::arg("bias"),
+        py::arg("m"), py::arg("n"), py::arg("k"), py::arg("layout"),
+        py::arg("splits") = 1, py::arg("workspace") = 0,
+        py::arg("stream") = 0, py::arg("xcd_swizzle") = 0,
+        "C bf16 = bf16(op(A) @ op(B) + bias[n]); layout nt | nn | tn | tt, "
+        "bias 0 = none; workspace [splits][M][N] fp32 when splits > 1");
+  m.def("gemm_out_lds_offset", &hpk::gemm_out_lds_offset, py::arg("row"),
+        py::arg("col"),
+        "byte offset of tile element (row, col) in the staged bf16 output "
+        "tile; the function the kernels call");
+  m.def("gemm_out_read",
+        [](int t, int p, int i) {
+          hpk::GemmOutRead r = hpk::gemm_out_read(t, p, i);
+          return py::make_tuple(r.row, r.col);
+        },
+        py::arg("t"), py::arg("p"), py::arg("i"),
+        "(row, col) of the first element of 16-byte LDS read i of thread t "
+        "in pass p of the bf16 store loop; the function the kernels call");
+  m.def("colsum_bf16",
+        [](uintptr_t out, uintptr_t x, long m, long n, int chunks,
+           uintptr_t workspace, uintptr_t stream) {
+          hpk::launch_colsum_bf16(reinterpret_cast<float*>(out),
+                                  reinterpret_cast<const void*>(x), m, n,
+                                  chunks, reinterpret_cast<void*>(workspace),
+                                  as_stream(stream));
+        },
+        py::arg("out"), py::arg("x"), py::arg("m"), py::arg("n"),
+        py::arg("chunks") = 1, py::arg("workspace") = 0,
+        py::arg("stream") = 0,
+        "out[n] = sum_m x[m,n], x bf16 [m,n]; chunks > 1 needs a workspace "
+        "of chunks * colsum_pitch(n) floats and colsum_pitch(n) floats in out");
+  m.def("colsum_rows",
+        [](long m, int chunks, int r) {
+          if (m < 1 || chunks < 1 || chunks > m || r < 0 || r >= chunks)
+            throw py::value_error("need 1 <= chunks <= M and 0 <= r < chunks");
+          hpk::SplitKRange s = hpk::colsum_rows(m, chunks, r);
+          return py::make_tuple(s.first, s.count);
+        },
+        py::arg("m"), py::arg("chunks"), py::arg("r"),
+        "(first, count): the rows chunk r of `chunks` sums; the function the "
+        "kernel calls");
+  m.def("colsum_pitch", &hpk::colsum_pitch, py::arg("n"));
+  m.def("colsum_plan", &hpk::colsum_plan, py::arg("m"), py::arg("n"),
+        py::arg("n_cu"),
+        "row chunks colsum_bf16 uses for an [m, n] input on n_cu compute "
+        "units; pure host function");
+  m.attr("COLSUM_MIN_ROWS") = hpk::kColsumMinRows;
+  m.attr("COLSUM_MAX_CHUNKS") = hpk::kColsumMaxChunks;
   m.attr("SPLITK_MIN_TILES") = hpk::kSplitKMinTiles;
   m.attr("SPLITK_MAX_SPLITS") = hpk::kSplitKMaxSplits;
   m.attr("SPLITK_REDUCE_MAX_GRID") = hpk::kSplitKReduceMaxGrid;

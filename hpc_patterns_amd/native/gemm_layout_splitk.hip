@@ -237,4 +237,50 @@ void launch_gemm_bf16_layout_splitk(float* C, const void* A, const void* B,
       workspace, stream, xcd_swizzle);
 }
 
+// The tile kernel alone, for a caller that folds the slices itself
+// (gemm_epilogue.hip: fold, bias and bf16 conversion in one pass).
+void launch_gemm_bf16_layout_splitk_partials(float* workspace, const void* A,
+                                             const void* B, long M, long N,
+                                             long K, const char* layout,
+                                             int splits, hipStream_t stream,
+                                             int xcd_swizzle) {
+  const std::string lay = layout ? layout : "";
+  if (lay != "nn" && lay != "tn" && lay != "tt")
+    throw std::invalid_argument("gemm_bf16_layout_splitk_partials: unknown "
+                                "layout '" + lay + "' (nn|tn|tt)");
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM != 0 || N % BN != 0 ||
+      K % BK != 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
+    throw std::runtime_error("gemm_bf16_layout_splitk_partials requires "
+                             "M,N % 128 == 0 and K % 64 == 0");
+  if (splits < 2 || splits > K / BK || splits > 65535)
+    throw std::runtime_error("gemm_bf16_layout_splitk_partials requires "
+                             "2 <= splits <= K / 64");
+  if (workspace == nullptr || A == nullptr || B == nullptr)
+    throw std::runtime_error("gemm_bf16_layout_splitk_partials: null operand");
+  if ((uintptr_t)A % 16 != 0 || (uintptr_t)B % 16 != 0 ||
+      (uintptr_t)workspace % 16 != 0)
+    throw std::runtime_error("gemm_bf16_layout_splitk_partials requires A, B "
+                             "and the workspace on 16-byte boundaries");
+  const char* genv = std::getenv("HPK_GEMM_GROUP");
+  const int group = genv ? std::atoi(genv) : 1;
+  const int tiles_n = (int)(N / BN);
+  const int nwg = (int)(M / BM) * tiles_n;
+  const dim3 grid(nwg, splits);
+  const __hip_bfloat16* a = (const __hip_bfloat16*)A;
+  const __hip_bfloat16* b = (const __hip_bfloat16*)B;
+  if (lay == "nn")
+    hipLaunchKernelGGL((k_gemm_bf16_lay_splitk<false, true>), grid, dim3(512),
+                       0, stream, workspace, a, b, (int)M, (int)N, (int)K,
+                       splits, tiles_n, nwg, xcd_swizzle, group);
+  else if (lay == "tn")
+    hipLaunchKernelGGL((k_gemm_bf16_lay_splitk<true, true>), grid, dim3(512),
+                       0, stream, workspace, a, b, (int)M, (int)N, (int)K,
+                       splits, tiles_n, nwg, xcd_swizzle, group);
+  else
+    hipLaunchKernelGGL((k_gemm_bf16_lay_splitk<true, false>), grid, dim3(512),
+                       0, stream, workspace, a, b, (int)M, (int)N, (int)K,
+                       splits, tiles_n, nwg, xcd_swizzle, group);
+  check_hip(hipGetLastError(), "launch_gemm_bf16_layout_splitk_partials");
+}
+
 } // namespace hpk

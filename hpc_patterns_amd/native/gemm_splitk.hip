@@ -265,6 +265,34 @@ void launch_splitk(const char* kind, typename Tr::Out* C, const void* A,
                      nvec, splits, stream);
 }
 
+// The tile kernel alone, for a caller that folds the slices itself
+// (gemm_epilogue.hip: fold, bias and bf16 conversion in one pass). A
+// template like launch_splitk, so that the kernels keep their order in the
+// code object.
+template <class Tr>
+void launch_partials(const char* what, typename Tr::Out* workspace,
+                     const void* A, const void* B, long M, long N, long K,
+                     int splits, hipStream_t stream, int xcd_swizzle) {
+  const std::string w = what;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM != 0 || N % BN != 0 ||
+      K % BK != 0)
+    throw std::runtime_error(w + " requires M,N % 128 == 0 and K % 64 == 0");
+  if (splits < 2 || splits > K / BK || splits > 65535)
+    throw std::runtime_error(w + " requires 2 <= splits <= K / 64");
+  if (workspace == nullptr || (uintptr_t)workspace % 16 != 0)
+    throw std::runtime_error(w + " requires a workspace on a 16-byte "
+                                 "boundary");
+  const char* genv = std::getenv("HPK_GEMM_GROUP");
+  const int group = genv ? std::atoi(genv) : 1;
+  const int tiles_n = (int)(N / BN);
+  const int nwg = (int)(M / BM) * tiles_n;
+  hipLaunchKernelGGL(k_gemm_splitk_nt<Tr>, dim3(nwg, splits), dim3(512), 0,
+                     stream, workspace, (const typename Tr::In*)A,
+                     (const typename Tr::In*)B, (int)M, (int)N, (int)K, splits,
+                     tiles_n, nwg, xcd_swizzle, group);
+  check_hip(hipGetLastError(), ("launch_" + w).c_str());
+}
+
 } // namespace
 
 int gemm_splitk_plan(long M, long N, long K, int n_cu) {
@@ -316,6 +344,14 @@ void launch_gemm_splitk_i8_nt(int* C, const void* A, const void* B, long M,
                               hipStream_t stream, int xcd_swizzle) {
   launch_splitk<SkI8, i32x4>("i8", C, A, B, M, N, K, splits, workspace,
                              stream, xcd_swizzle);
+}
+
+void launch_gemm_splitk_bf16_nt_partials(float* workspace, const void* A,
+                                         const void* B, long M, long N, long K,
+                                         int splits, hipStream_t stream,
+                                         int xcd_swizzle) {
+  launch_partials<SkBf16>("gemm_splitk_bf16_nt_partials", workspace, A, B, M,
+                          N, K, splits, stream, xcd_swizzle);
 }
 
 } // namespace hpk

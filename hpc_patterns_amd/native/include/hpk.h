@@ -192,6 +192,85 @@ void launch_gemm_bf16_layout_splitk(float* C, const void* A, const void* B,
                                     void* workspace, hipStream_t stream,
                                     int xcd_swizzle = 0);
 
+// The split-K tile kernels alone (gemm_splitk.hip, gemm_layout_splitk.hip):
+// split s writes its fp32 partial to slice s of `workspace` and nothing
+// folds them — for launch_gemm_bf16_epilogue, whose fold also adds the bias
+// and converts. Shapes and alignment as the launchers above; splits >= 2.
+void launch_gemm_splitk_bf16_nt_partials(float* workspace, const void* A,
+                                         const void* B, long M, long N, long K,
+                                         int splits, hipStream_t stream,
+                                         int xcd_swizzle = 0);
+void launch_gemm_bf16_layout_splitk_partials(float* workspace, const void* A,
+                                             const void* B, long M, long N,
+                                             long K, const char* layout,
+                                             int splits, hipStream_t stream,
+                                             int xcd_swizzle = 0);
+
+// bf16 output with bias (gemm_epilogue.hip): C[M,N] bf16 row-major =
+// bf16(op(A) @ op(B) + bias[n]) for layout nt | nn | tn | tt (operands as
+// stored, as above). The bodies are k_gemm_bf16_nt_db<2,4> and
+// k_gemm_bf16_lay with another epilogue: one fp32 add of bias[n] (fp32 [N];
+// nullptr = no add at all), one round-to-nearest-even conversion, the
+// 128x128 bf16 tile staged through the K loop's LDS and written as whole
+// 256-byte rows. The accumulators are those of bf16_db8, so the result is
+// bf16(c32 + bias) of the fp32 kernels bit for bit. splits > 1: the
+// existing split-K tile kernels write fp32 partials to `workspace`
+// ([splits][M][N] fp32) and one fold kernel computes
+// bf16((((P0 + P1) + P2) + ...) + bias[n]). Contract: docs/gemm.md, "bf16
+// output and bias". Throws std::invalid_argument on an unknown layout,
+// std::runtime_error unless M,N % 128 == 0, K % 64 == 0,
+// 1 <= splits <= min(K / 64, 65535), A, B, C (and the workspace when
+// splits > 1) on 16-byte boundaries.
+void launch_gemm_bf16_epilogue(void* C, const void* A, const void* B,
+                               const float* bias, long M, long N, long K,
+                               const char* layout, int splits, void* workspace,
+                               hipStream_t stream, int xcd_swizzle = 0);
+// Byte offset, in the staged 128x128 bf16 tile (32 KiB), of element
+// (row, col): rows 2p and 2p+1 of a column share a dword (one
+// v_cvt_pk_bf16_f32 result, one ds_write_b32), a row pair is 512 bytes, and
+// the 16-byte chunk (4 columns) index is XORed with 4 * ((p >> 1) & 1) so
+// that the two 16-lane halves of a write land on different banks. The
+// kernel, and the bank enumeration in tests/test_gemm_epilogue_logic.py,
+// call this function.
+__host__ __device__ inline int gemm_out_lds_offset(int row, int col) {
+  const int p = row >> 1;
+  const int chunk = (col >> 2) ^ (((p >> 1) & 1) << 2);
+  return 512 * p + 16 * chunk + 4 * (col & 3) + 2 * (row & 1);
+}
+// Tile (row, col) of the first element of 16-byte LDS read i (0 | 1) of
+// thread t (0..511) in pass p (0 | 1) of the store loop: the thread owns
+// columns 8 * (t & 15) .. +7 of rows `row` and `row + 1`; lanes 8..15 of a
+// row take their odd chunk first, so 16 lanes cover all 16 bank windows.
+struct GemmOutRead {
+  int row, col;
+};
+__host__ __device__ inline GemmOutRead gemm_out_read(int t, int p, int i) {
+  return {2 * (32 * p + (t >> 4)), 4 * (2 * (t & 15) + (i ^ ((t >> 3) & 1)))};
+}
+
+// Column sums of a bf16 matrix (gemm_epilogue.hip): out[n] = sum_m x[m,n],
+// the bias gradient of a linear layer. x [M,N] bf16 contiguous, N % 8 == 0,
+// 16-byte aligned; out fp32. Row chunk r of R sums rows colsum_rows(M, R, r)
+// in ascending order in fp32; R == 1 writes `out`, else chunk r writes
+// workspace[r * colsum_pitch(N) ..] and launch_splitk_reduce_f32 folds the
+// R rows in ascending r into `out`, which then must hold colsum_pitch(N)
+// floats (only the first N mean anything). Same bits on every run for the
+// same (M, N, R). Throws std::runtime_error unless 1 <= R <= min(M, 65535),
+// N % 8 == 0, x and out (and the workspace) on 16-byte boundaries.
+__host__ __device__ inline SplitKRange colsum_rows(long M, int R, int r) {
+  return gemm_splitk_ktiles(M, R, r);
+}
+inline long colsum_pitch(long N) { return (N + 1023) / 1024 * 1024; }
+// Row chunks the front door uses (pure host): enough 64-thread workgroups
+// for kColsumWavesPerCu waves per compute unit, at least kColsumMinRows
+// rows per chunk, at most kColsumMaxChunks chunks.
+constexpr int kColsumWavesPerCu = 16;
+constexpr int kColsumMinRows = 32;
+constexpr int kColsumMaxChunks = 256;
+int colsum_plan(long M, long N, int n_cu);
+void launch_colsum_bf16(float* out, const void* x, long M, long N, int R,
+                        void* workspace, hipStream_t stream);
+
 // MX quantize (quant.hip): the convert-to-MX step that makes the two MX
 // GEMMs' operands from real data. x is [rows][K] contiguous fp32 (or bf16
 // when x_is_bf16), K % 32 == 0; every 32 consecutive elements along K get

@@ -875,8 +875,199 @@ def _check_split_k(split_k, ints: bool):
                      f"'auto'; got {split_k!r}")
 
 
+def _check_out_dtype_bias(out_dtype, bias):
+    """out_dtype and bias of matmul, on their type and value alone: before
+    any tensor is looked at"""
+    if out_dtype is not None and out_dtype is not torch.bfloat16:
+        raise ValueError(f"out_dtype must be None or torch.bfloat16; got "
+                         f"{out_dtype!r}")
+    if bias is not None and not isinstance(bias, torch.Tensor):
+        raise TypeError(f"bias must be None or a tensor; got "
+                        f"{type(bias).__name__}")
+    if bias is not None and out_dtype is None:
+        raise ValueError("bias needs out_dtype=torch.bfloat16: an fp32 output "
+                         "with a bias is not built")
+
+
+def _bias_f32(bias, n: int, n_padded: int, device):
+    """bias [n] (bf16 or fp32) -> contiguous fp32 [n_padded], zero-padded;
+    bf16 -> fp32 is exact"""
+    if bias.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"bias must be bfloat16 or float32, got {bias.dtype}")
+    if bias.dim() != 1 or bias.shape[0] != n:
+        raise ValueError(f"bias must have shape ({n},); got "
+                         f"{tuple(bias.shape)}")
+    if bias.device != device:
+        raise TypeError(f"bias is on {bias.device}, the operands on {device}")
+    bias = bias.float().contiguous()
+    if n_padded == n:
+        return bias
+    out = torch.zeros(n_padded, dtype=torch.float32, device=device)
+    out[:n] = bias
+    return out
+
+
+def gemm_bf16_epilogue(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                       layout: str = "nt", bias: torch.Tensor = None,
+                       splits: int = 1, workspace: torch.Tensor = None,
+                       stream=None, xcd_swizzle: bool = False) -> None:
+    """K7 with a bf16 output: C[M,N] bf16 = bf16(op(A) @ op(B) + bias[n]),
+    written by the GEMM kernel itself (native/gemm_epilogue.hip) — no fp32 C
+    in HBM and no elementwise pass behind it.
+
+        layout  a        b
+        "nt"    [M,K]    [N,K]
+        "nn"    [M,K]    [K,N]
+        "tn"    [K,M]    [K,N]
+        "tt"    [K,M]    [N,K]
+
+    The products are those of the double-buffered 128^2 kernels
+    (gemm_bf16 under HPK_GEMM_VARIANT=db, gemm_bf16_layout): the result is
+    (c32 + bias).to(bfloat16) of their fp32 C bit for bit — one fp32 add,
+    one round-to-nearest-even conversion, the bias never rounded first.
+    bias is fp32 [N], contiguous, on c's device; None adds nothing at all.
+    splits > 1 runs the split-K tile kernels of gemm_splitk /
+    gemm_bf16_layout_splitk into workspace ([splits, M, N] fp32; None
+    allocates) and one fold kernel that sums the partials in ascending s,
+    adds the bias and converts. Requires M,N % 128 == 0, K % 64 == 0,
+    1 <= splits <= K/64 and a, b, c on 16-byte boundaries (matmul pads).
+    """
+    if layout != "nt" and layout not in _LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}; expected one of "
+                         f"'nn', 'tn', 'tt', 'nt'")
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+        if a.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8):
+            raise TypeError("only bf16 operands have a bf16 output: fp8, "
+                            "int8 and MX outputs are not built")
+        raise TypeError("c, a and b must be bf16")
+    if c.dtype != torch.bfloat16:
+        raise TypeError("c, a and b must be bf16")
+    for t, name in ((c, "c"), (a, "a"), (b, "b")):
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise TypeError(f"{name} must be a contiguous 2-D CUDA tensor")
+    a_t, b_n = _LAYOUTS.get(layout, (False, False))
+    k, m = a.shape if a_t else a.shape[::-1]
+    kb, n = b.shape if b_n else b.shape[::-1]
+    if kb != k or c.shape != (m, n):
+        raise ValueError(f"shape mismatch for layout {layout}: "
+                         f"A{tuple(a.shape)} B{tuple(b.shape)} "
+                         f"C{tuple(c.shape)}")
+    if m < 128 or n < 128 or k < 64 or m % 128 or n % 128 or k % 64:
+        raise ValueError(f"gemm_bf16_epilogue requires M,N % 128 == 0 and "
+                         f"K % 64 == 0; got M={m} N={n} K={k}")
+    for t, name in ((a, "a"), (b, "b"), (c, "c")):
+        if t.data_ptr() % 16 != 0:
+            raise ValueError(f"{name} must start on a 16-byte boundary")
+    bias_ptr = 0
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 \
+                or not bias.is_contiguous() or bias.device != c.device:
+            raise TypeError("bias must be a contiguous float32 tensor on c's "
+                            "device")
+        if bias.dim() != 1 or bias.shape[0] != n:
+            raise ValueError(f"bias must have shape ({n},); got "
+                             f"{tuple(bias.shape)}")
+        bias_ptr = bias.data_ptr()
+    splits = int(splits)
+    if not 1 <= splits <= k // 64:
+        raise ValueError(f"need 1 <= splits <= K/64 = {k // 64}; got {splits}")
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda \
+                or not workspace.is_contiguous() \
+                or workspace.dtype != torch.float32:
+            raise TypeError("workspace must be a contiguous float32 CUDA "
+                            "tensor")
+        if workspace.numel() < splits * m * n:
+            raise ValueError(f"workspace holds {workspace.numel()} elements; "
+                             f"{splits} x {m} x {n} are needed")
+        if workspace.data_ptr() % 16 != 0:
+            raise ValueError("workspace must start on a 16-byte boundary")
+    ws_ptr = 0
+    if splits > 1:
+        if workspace is None:
+            workspace = torch.empty(splits, m, n, dtype=torch.float32,
+                                    device=c.device)
+            if hasattr(stream, "cuda_stream"):
+                # allocated on the current stream, used on another
+                workspace.record_stream(stream)
+        ws_ptr = workspace.data_ptr()
+    native().gemm_bf16_epilogue(
+        c.data_ptr(), a.data_ptr(), b.data_ptr(), bias_ptr, m, n, k, layout,
+        splits, ws_ptr, _stream_handle(stream), int(xcd_swizzle))
+
+
+def colsum_plan(m: int, n: int, n_cu: int = None) -> int:
+    """Row chunks colsum_bf16 cuts an [m, n] input into: enough 64-thread
+    workgroups (one thread per 8 columns) for COLSUM waves on every compute
+    unit, at least 32 rows per chunk, at most 256 chunks (docs/gemm.md,
+    "bf16 output and bias"). n_cu=None reads the current device."""
+    if n_cu is None:
+        n_cu = _device_cu_count(torch.cuda.current_device())
+    return native().colsum_plan(int(m), int(n), int(n_cu))
+
+
+def colsum_bf16(x: torch.Tensor, out: torch.Tensor = None,
+                stream=None) -> torch.Tensor:
+    """out[n] = sum_m x[m, n] in fp32 for a bf16 [M, N] contiguous CUDA
+    tensor (native/gemm_epilogue.hip): the bias gradient of linear_bf16.
+
+    The rows are cut into colsum_plan(M, N) chunks; chunk r sums its rows
+    in ascending order in fp32, and the chunk sums are folded in ascending
+    r (the split-K fold kernel), so the result is the same bits on every
+    run for the same shape on the same device. N is zero-padded to a
+    multiple of 8 (a copy) when it is not one. out: None allocates; a
+    caller's must be a contiguous fp32 CUDA tensor of shape (N,). Returns
+    the sums, shape (N,).
+    """
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise TypeError("x must be a CUDA tensor")
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError("x must be a contiguous 2-D bfloat16 tensor")
+    m, n = x.shape
+    if m < 1 or n < 1:
+        raise ValueError(f"need M >= 1 and N >= 1; got {tuple(x.shape)}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda \
+                or out.dtype != torch.float32 or not out.is_contiguous():
+            raise TypeError("out must be a contiguous float32 CUDA tensor")
+        if out.shape != (n,):
+            raise ValueError(f"out must have shape ({n},); got "
+                             f"{tuple(out.shape)}")
+    n8 = -(-n // 8) * 8
+    xp = _pad2d(x, m, n8)
+    if xp.data_ptr() % 16 != 0:
+        xp = xp.clone()
+    chunks = colsum_plan(m, n8)
+    lib = native()
+    pitch = lib.colsum_pitch(n8)
+    # the kernel writes n8 sums, the fold of chunks > 1 a whole pitch
+    width = n8 if chunks == 1 else pitch
+    direct = out is not None and width == n and out.data_ptr() % 16 == 0
+    buf = torch.empty(width * (0 if direct else 1)
+                      + (pitch * chunks if chunks > 1 else 0),
+                      dtype=torch.float32, device=x.device)
+    if hasattr(stream, "cuda_stream"):
+        buf.record_stream(stream)
+        xp.record_stream(stream)
+    res = out if direct else buf[:width]
+    ws_ptr = buf[0 if direct else width:].data_ptr() if chunks > 1 else 0
+    lib.colsum_bf16(res.data_ptr(), xp.data_ptr(), m, n8, chunks, ws_ptr,
+                    _stream_handle(stream))
+    if direct:
+        return out
+    if out is not None:
+        if hasattr(stream, "cuda_stream"):
+            with torch.cuda.stream(stream):
+                out.copy_(buf[:n])
+        else:
+            out.copy_(buf[:n])
+        return out
+    return buf[:n]
+
+
 def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
-           xcd_swizzle: bool = False, split_k=None) -> torch.Tensor:
+           xcd_swizzle: bool = False, split_k=None, out_dtype=None,
+           bias: torch.Tensor = None) -> torch.Tensor:
     """Layout-agnostic front door: returns the logical a [M,K] @ b [K,N].
 
     The layout is read from the strides (matmul_layout: row-major or a
@@ -898,11 +1089,53 @@ def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
     ValueError); "auto" asks gemm_splitk_plan(m, n, k): a small output with
     a long sum — dW = dy^T x over many tokens — takes the split path,
     everything the plan answers 1 for keeps the path above.
+
+    out_dtype=torch.bfloat16 (bf16 operands only) returns bf16, rounded once
+    from the fp32 accumulators by the GEMM kernel itself, in all four
+    layouts, nt included: gemm_bf16_epilogue on the tensors padded as
+    above, i.e. the double-buffered 128^2 kernels, not matmul_nt's 256^2
+    one. bias ([N], bf16 or fp32; a bf16 one is widened, which is exact) is
+    added in fp32 before that one rounding; it is zero-padded with N. A
+    bias without out_dtype=torch.bfloat16 is a ValueError. split_k works as
+    above; a plan of 1 takes the kernel without a split. out_dtype and bias
+    are checked with split_k, before any tensor.
     """
     _check_split_k(split_k, ints=True)
+    _check_out_dtype_bias(out_dtype, bias)
     layout, a_st, b_st = matmul_layout(a, b)
     if a.dtype != b.dtype:
         raise TypeError(f"a is {a.dtype}, b is {b.dtype}")
+    if out_dtype is not None:
+        if a.dtype != torch.bfloat16:
+            raise TypeError(f"out_dtype=torch.bfloat16 takes bf16 operands; "
+                            f"got {a.dtype}")
+        m, k = a.shape
+        n = b.shape[1]
+        mp, np_, kp = gemm_layout_pad_shapes(m, n, k)
+        a_t, b_n = _LAYOUTS.get(layout, (False, False))
+        splits = 1
+        if split_k == "auto":
+            splits = gemm_splitk_plan(m, n, k)
+        elif split_k is not None:
+            if not 1 <= split_k <= kp // 64:
+                raise ValueError(f"need 1 <= split_k <= K_padded/64 = "
+                                 f"{kp // 64} (K = {k} padded to {kp}); got "
+                                 f"{split_k}")
+            splits = split_k
+        bias_p = None if bias is None else _bias_f32(bias, n, np_, a.device)
+
+        def operand(t, rows, cols):
+            t = _pad2d(t, rows, cols)
+            return t if t.data_ptr() % 16 == 0 else t.clone()
+
+        ap = operand(a_st, *((kp, mp) if a_t else (mp, kp)))
+        bp = operand(b_st, *((kp, np_) if b_n else (np_, kp)))
+        c = torch.empty(mp, np_, dtype=torch.bfloat16, device=a.device)
+        gemm_bf16_epilogue(c, ap, bp, layout, bias=bias_p, splits=splits,
+                           stream=stream, xcd_swizzle=xcd_swizzle)
+        if (mp, np_) == (m, n):
+            return c
+        return c[:m, :n].contiguous()
     if layout == "nt":
         return matmul_nt(a_st, b_st, stream=stream, xcd_swizzle=xcd_swizzle,
                          split_k=split_k)
@@ -963,11 +1196,64 @@ class _LinearBf16(torch.autograd.Function):
         return dx, dw, None
 
 
-def linear_bf16(x: torch.Tensor, w: torch.Tensor,
-                split_k=None) -> torch.Tensor:
-    """y = x @ w^T for bf16 x [M,K] and w [N,K], differentiable; every
-    product runs on the K7 kernels with fp32 accumulation and is cast to
-    bf16, and nothing is transposed in memory:
+class _LinearBf16Bias(torch.autograd.Function):
+    """_LinearBf16 with a bias through torch elementwise ops: the composition
+    the fused path replaces, kept as its A/B row and its oracle"""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, split_k):
+        ctx.save_for_backward(x, w)
+        ctx.split_k = split_k
+        ctx.bias_dtype = bias.dtype
+        return (matmul_nt(x, w, split_k=split_k)
+                + bias.float()).to(torch.bfloat16)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        sk = ctx.split_k
+        if not dy.is_contiguous():
+            dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = matmul(dy, w, split_k=sk).to(torch.bfloat16)
+        if ctx.needs_input_grad[1]:
+            dw = matmul(dy.t(), x, split_k=sk).to(torch.bfloat16)
+        if ctx.needs_input_grad[2]:
+            db = dy.float().sum(0).to(ctx.bias_dtype)
+        return dx, dw, db, None
+
+
+class _LinearBf16Fused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, split_k):
+        ctx.save_for_backward(x, w)
+        ctx.split_k = split_k
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return matmul(x, w.t(), split_k=split_k, out_dtype=torch.bfloat16,
+                      bias=bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        sk = ctx.split_k
+        if not dy.is_contiguous():  # e.g. the expanded scalar of sum()
+            dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:     # nn: dy [M,N] w [N,K]
+            dx = matmul(dy, w, split_k=sk, out_dtype=torch.bfloat16)
+        if ctx.needs_input_grad[1]:     # tn: dy [M,N] x [M,K]
+            dw = matmul(dy.t(), x, split_k=sk, out_dtype=torch.bfloat16)
+        if ctx.bias_dtype is not None and ctx.needs_input_grad[2]:
+            db = colsum_bf16(dy).to(ctx.bias_dtype)
+        return dx, dw, db, None
+
+
+def linear_bf16(x: torch.Tensor, w: torch.Tensor, split_k=None,
+                bias: torch.Tensor = None, fused=None) -> torch.Tensor:
+    """y = x @ w^T (+ bias) for bf16 x [M,K] and w [N,K], differentiable;
+    every product runs on the K7 kernels with fp32 accumulation and comes
+    out in bf16, and nothing is transposed in memory:
 
         forward   y  = matmul_nt(x, w)       nt
         backward  dx = matmul(dy, w)         nn
@@ -982,8 +1268,30 @@ def linear_bf16(x: torch.Tensor, w: torch.Tensor,
     it possibly the last bit of the result, then differs from the default's.
     split_k is None (the default: no split anywhere) or "auto"; anything
     else is a ValueError.
+
+    Without bias and fused this is the path above: fp32 products, each
+    followed by a torch cast to bf16. bias ([N], bf16 or fp32) and fused
+    choose the fused products (matmul(out_dtype=torch.bfloat16)): the GEMM
+    kernels add the bias in fp32 and write bf16 themselves, the split
+    products fold, add and convert in one kernel, and dbias is
+    colsum_bf16(dy) cast to the bias's dtype; only the gradients asked for
+    are computed. fused=None means fused iff a bias is given; True fuses
+    without a bias; False with a bias runs the fp32 products plus torch
+    elementwise ops (add, cast, and a torch column sum), the composition
+    the fusion replaces. The fused forward runs the double-buffered 128^2
+    kernel where the default runs the 256^2 8-phase one: on random data its
+    last bit may differ from the default's (another fp32 summation order),
+    for the same reason split_k="auto" may. Measured (docs/gemm.md, "bf16
+    output and bias"): the 256^2 kernel plus add and cast is behind the
+    fused call up to 4096^3 and level with it at 8192^3, the largest size
+    swept.
     """
     _check_split_k(split_k, ints=False)
+    if fused is not None and not isinstance(fused, bool):
+        raise ValueError(f"fused must be None, True or False; got {fused!r}")
+    if bias is not None and not isinstance(bias, torch.Tensor):
+        raise TypeError(f"bias must be None or a tensor; got "
+                        f"{type(bias).__name__}")
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
         raise ValueError(f"need x[M,K], w[N,K]; got x{tuple(x.shape)} "
                          f"w{tuple(w.shape)}")
@@ -991,4 +1299,15 @@ def linear_bf16(x: torch.Tensor, w: torch.Tensor,
         raise TypeError("x and w must be bf16")
     if not x.is_contiguous() or not w.is_contiguous():
         raise TypeError("x and w must be contiguous")
-    return _LinearBf16.apply(x, w, split_k)
+    if bias is None and not fused:
+        return _LinearBf16.apply(x, w, split_k)
+    if bias is not None:
+        if bias.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"bias must be bfloat16 or float32, got "
+                            f"{bias.dtype}")
+        if bias.dim() != 1 or bias.shape[0] != w.shape[0]:
+            raise ValueError(f"bias must have shape ({w.shape[0]},); got "
+                             f"{tuple(bias.shape)}")
+    if fused is False:
+        return _LinearBf16Bias.apply(x, w, bias, split_k)
+    return _LinearBf16Fused.apply(x, w, bias, split_k)
