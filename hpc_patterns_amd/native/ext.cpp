@@ -218,6 +218,31 @@ PYBIND11_MODULE(_hpk, m) {
         py::arg("stream") = 0, py::arg("xcd_swizzle") = 0,
         "C bf16 = bf16(op(A) @ op(B) + bias[n]); layout nt | nn | tn | tt, "
         "bias 0 = none; workspace [splits][M][N] fp32 when splits > 1");
+  m.def("gemm_bf16_act",
+        [](uintptr_t c, uintptr_t aux, uintptr_t a, uintptr_t b,
+           uintptr_t bias, long m, long n, long k, const std::string& layout,
+           int act, int mode, int splits, uintptr_t workspace,
+           uintptr_t stream, int xcd_swizzle) {
+          hpk::launch_gemm_bf16_act(
+              reinterpret_cast<void*>(c), reinterpret_cast<void*>(aux),
+              reinterpret_cast<const void*>(a),
+              reinterpret_cast<const void*>(b),
+              reinterpret_cast<const float*>(bias), m, n, k, layout.c_str(),
+              act, mode, splits, reinterpret_cast<void*>(workspace),
+              as_stream(stream), xcd_swizzle);
+        },
+        py::arg("c"), py::arg("aux"), py::arg("a"), py::arg("b"),
+        py::arg("bias"), py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("layout"), py::arg("act"), py::arg("mode"),
+        py::arg("splits") = 1, py::arg("workspace") = 0,
+        py::arg("stream") = 0, py::arg("xcd_swizzle") = 0,
+        "mode ACT_FORWARD: C bf16 = bf16(act(op(A) @ op(B) + bias[n])), aux "
+        "(0 = none) receives the bf16 pre-activation; mode ACT_GRAD: C = "
+        "bf16((op(A) @ op(B)) * act'(aux)); act ACT_RELU | ACT_GELU (tanh)");
+  m.attr("ACT_RELU") = (int)hpk::kActRelu;
+  m.attr("ACT_GELU") = (int)hpk::kActGelu;
+  m.attr("ACT_FORWARD") = (int)hpk::kActForward;
+  m.attr("ACT_GRAD") = (int)hpk::kActGrad;
   m.def("gemm_out_lds_offset", &hpk::gemm_out_lds_offset, py::arg("row"),
         py::arg("col"),
         "byte offset of tile element (row, col) in the staged bf16 output "

@@ -248,6 +248,29 @@ __host__ __device__ inline GemmOutRead gemm_out_read(int t, int p, int i) {
   return {2 * (32 * p + (t >> 4)), 4 * (2 * (t & 15) + (i ^ ((t >> 3) & 1)))};
 }
 
+// Activation epilogues (gemm_act.hip): the kernels above with relu or the
+// tanh-form gelu behind the accumulators, layout nt | nn | tn | tt.
+//   kActForward: z = acc + bias[n] in fp32 (nullptr = no add), C[M,N] =
+//     bf16(act(z)); aux, when non-null, receives bf16(z) [M,N] — bit for bit
+//     what launch_gemm_bf16_epilogue writes.
+//   kActGrad: C[M,N] = bf16(acc * act'(aux)), aux a bf16 [M,N] tensor (the
+//     forward's z for gelu, its output or z for relu: act' = aux > 0); one
+//     fp32 multiply before the one rounding. No bias.
+// splits > 1: the split-K tile kernels write fp32 partials to `workspace`
+// ([splits][M][N] fp32) and one fold kernel applies the same mode. The
+// arithmetic, its error bound and the special values: docs/gemm.md,
+// "Activations". Throws as launch_gemm_bf16_epilogue does (aux too must be
+// on a 16-byte boundary); std::invalid_argument on an unknown activation
+// or mode; std::runtime_error when kActGrad comes without aux or with a
+// bias.
+enum GemmAct { kActRelu = 0, kActGelu = 1 };
+enum GemmActMode { kActForward = 0, kActGrad = 1 };
+void launch_gemm_bf16_act(void* C, void* aux, const void* A, const void* B,
+                          const float* bias, long M, long N, long K,
+                          const char* layout, int act, int mode, int splits,
+                          void* workspace, hipStream_t stream,
+                          int xcd_swizzle = 0);
+
 // Column sums of a bf16 matrix (gemm_epilogue.hip): out[n] = sum_m x[m,n],
 // the bias gradient of a linear layer. x [M,N] bf16 contiguous, N % 8 == 0,
 // 16-byte aligned; out fp32. Row chunk r of R sums rows colsum_rows(M, R, r)

@@ -1065,9 +1065,200 @@ def colsum_bf16(x: torch.Tensor, out: torch.Tensor = None,
     return buf[:n]
 
 
+ACTIVATIONS = ("relu", "gelu")
+_SQRT_2_OVER_PI = 0.7978845608028654
+
+
+def _check_activation_name(act, what: str):
+    if not isinstance(act, str) or act not in ACTIVATIONS:
+        raise ValueError(f"{what} must be one of {ACTIVATIONS} (gelu is the "
+                         f"tanh form; the erf form is not built); got "
+                         f"{act!r}")
+
+
+def _gelu_sigmoids(z: torch.Tensor):
+    """(s, 1 - s) of the tanh GELU in float64: s = 1 / (1 + exp(-2u)),
+    u = sqrt(2/pi) (z + 0.044715 z^3); 1 - s as 1 / (1 + exp(2u)), which
+    does not cancel"""
+    u2 = 2.0 * _SQRT_2_OVER_PI * (z + 0.044715 * z * z * z)
+    return 1.0 / (1.0 + torch.exp(-u2)), 1.0 / (1.0 + torch.exp(u2))
+
+
+def activation_reference(z: torch.Tensor, act: str) -> torch.Tensor:
+    """act(z) in float64, pure torch, any device: the reference of the
+    activation epilogues. relu: z where z > 0, NaN where z is NaN, else 0.
+    gelu: z * s with s = 1 / (1 + exp(-2u)), u = sqrt(2/pi) (z + 0.044715
+    z^3) — torch.nn.functional.gelu(approximate="tanh") in its sigmoid form,
+    special values included (gelu(-Inf) is NaN there too)."""
+    _check_activation_name(act, "act")
+    z = z.double()
+    if act == "relu":
+        return torch.where(z > 0, z, torch.where(torch.isnan(z), z,
+                                                 torch.zeros_like(z)))
+    return z * _gelu_sigmoids(z)[0]
+
+
+def activation_grad_terms(z: torch.Tensor, act: str):
+    """(first, second) with act'(z) = first + second, float64: gelu' =
+    s + z s (1 - s) 2 sqrt(2/pi) (1 + 0.134145 z^2); relu' = (z > 0) + 0.
+    |first| + |second| is the T of the acceptance rule (docs/gemm.md)."""
+    _check_activation_name(act, "act")
+    z = z.double()
+    if act == "relu":
+        return (z > 0).double(), torch.zeros_like(z)
+    s, sc = _gelu_sigmoids(z)
+    return s, z * s * sc * (2.0 * _SQRT_2_OVER_PI) * (1.0 + 0.134145 * z * z)
+
+
+def activation_grad_reference(z: torch.Tensor, act: str) -> torch.Tensor:
+    """act'(z) in float64, pure torch, any device (activation_grad_terms
+    summed)."""
+    first, second = activation_grad_terms(z, act)
+    return first + second
+
+
+def gemm_bf16_act(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                  layout: str = "nt", activation: str = None,
+                  bias: torch.Tensor = None, aux_out: torch.Tensor = None,
+                  grad_aux: torch.Tensor = None, splits: int = 1,
+                  workspace: torch.Tensor = None, stream=None,
+                  xcd_swizzle: bool = False) -> None:
+    """K7 with an activation epilogue (native/gemm_act.hip), layouts and
+    shapes as gemm_bf16_epilogue. activation is "relu" or "gelu" (the tanh
+    form; the erf form is not built).
+
+    Forward (grad_aux is None): with z = op(A) @ op(B) + bias[n] in fp32,
+    c = bf16(act(z)); aux_out, a bf16 [M,N] tensor, also receives bf16(z) —
+    the bits gemm_bf16_epilogue writes — which is what the gelu backward
+    needs; relu needs none, its output carries the mask.
+
+    Gradient (grad_aux given): c = bf16((op(A) @ op(B)) * act'(grad_aux)),
+    grad_aux a bf16 [M,N] tensor: the forward's z for gelu, its output or z
+    for relu. One fp32 multiply before the one rounding. bias and aux_out
+    must be None.
+
+    relu is exact; gelu is within the relative error derived in
+    docs/gemm.md, "Activations". splits, workspace, stream, xcd_swizzle: as
+    gemm_bf16_epilogue.
+    """
+    _check_activation_name(activation, "activation")
+    grad = grad_aux is not None
+    if grad and (bias is not None or aux_out is not None):
+        raise ValueError("grad_aux chooses the gradient mode, which takes "
+                         "neither bias nor aux_out")
+    if layout != "nt" and layout not in _LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}; expected one of "
+                         f"'nn', 'tn', 'tt', 'nt'")
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 \
+            or c.dtype != torch.bfloat16:
+        raise TypeError("c, a and b must be bf16")
+    for t, name in ((c, "c"), (a, "a"), (b, "b")):
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise TypeError(f"{name} must be a contiguous 2-D CUDA tensor")
+    a_t, b_n = _LAYOUTS.get(layout, (False, False))
+    k, m = a.shape if a_t else a.shape[::-1]
+    kb, n = b.shape if b_n else b.shape[::-1]
+    if kb != k or c.shape != (m, n):
+        raise ValueError(f"shape mismatch for layout {layout}: "
+                         f"A{tuple(a.shape)} B{tuple(b.shape)} "
+                         f"C{tuple(c.shape)}")
+    if m < 128 or n < 128 or k < 64 or m % 128 or n % 128 or k % 64:
+        raise ValueError(f"gemm_bf16_act requires M,N % 128 == 0 and "
+                         f"K % 64 == 0; got M={m} N={n} K={k}")
+    for t, name in ((a, "a"), (b, "b"), (c, "c")):
+        if t.data_ptr() % 16 != 0:
+            raise ValueError(f"{name} must start on a 16-byte boundary")
+    aux = grad_aux if grad else aux_out
+    aux_ptr = 0
+    if aux is not None:
+        name = "grad_aux" if grad else "aux_out"
+        if not isinstance(aux, torch.Tensor) or aux.dtype != torch.bfloat16 \
+                or not aux.is_contiguous() or aux.device != c.device:
+            raise TypeError(f"{name} must be a contiguous bfloat16 tensor on "
+                            f"c's device")
+        if aux.shape != (m, n):
+            raise ValueError(f"{name} must have shape ({m}, {n}); got "
+                             f"{tuple(aux.shape)}")
+        if aux.data_ptr() % 16 != 0:
+            raise ValueError(f"{name} must start on a 16-byte boundary")
+        if aux.data_ptr() == c.data_ptr():
+            raise ValueError(f"{name} and c must not be the same memory")
+        aux_ptr = aux.data_ptr()
+    bias_ptr = 0
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 \
+                or not bias.is_contiguous() or bias.device != c.device:
+            raise TypeError("bias must be a contiguous float32 tensor on c's "
+                            "device")
+        if bias.dim() != 1 or bias.shape[0] != n:
+            raise ValueError(f"bias must have shape ({n},); got "
+                             f"{tuple(bias.shape)}")
+        bias_ptr = bias.data_ptr()
+    splits = int(splits)
+    if not 1 <= splits <= k // 64:
+        raise ValueError(f"need 1 <= splits <= K/64 = {k // 64}; got {splits}")
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda \
+                or not workspace.is_contiguous() \
+                or workspace.dtype != torch.float32:
+            raise TypeError("workspace must be a contiguous float32 CUDA "
+                            "tensor")
+        if workspace.numel() < splits * m * n:
+            raise ValueError(f"workspace holds {workspace.numel()} elements; "
+                             f"{splits} x {m} x {n} are needed")
+        if workspace.data_ptr() % 16 != 0:
+            raise ValueError("workspace must start on a 16-byte boundary")
+    ws_ptr = 0
+    if splits > 1:
+        if workspace is None:
+            workspace = torch.empty(splits, m, n, dtype=torch.float32,
+                                    device=c.device)
+            if hasattr(stream, "cuda_stream"):
+                # allocated on the current stream, used on another
+                workspace.record_stream(stream)
+        ws_ptr = workspace.data_ptr()
+    lib = native()
+    lib.gemm_bf16_act(
+        c.data_ptr(), aux_ptr, a.data_ptr(), b.data_ptr(), bias_ptr, m, n, k,
+        layout, lib.ACT_RELU if activation == "relu" else lib.ACT_GELU,
+        lib.ACT_GRAD if grad else lib.ACT_FORWARD, splits, ws_ptr,
+        _stream_handle(stream), int(xcd_swizzle))
+
+
+def _check_activation_keywords(activation, return_aux, activation_grad,
+                               out_dtype, bias):
+    """activation, return_aux and activation_grad of matmul, on their type
+    and value alone: before any tensor is looked at"""
+    if activation is not None:
+        _check_activation_name(activation, "activation")
+    if not isinstance(return_aux, bool):
+        raise ValueError(f"return_aux must be True or False; got "
+                         f"{return_aux!r}")
+    if activation_grad is not None:
+        if not isinstance(activation_grad, tuple) or len(activation_grad) != 2:
+            raise ValueError("activation_grad must be None or a tuple (name, "
+                             "aux)")
+        _check_activation_name(activation_grad[0], "activation_grad's name")
+        if not isinstance(activation_grad[1], torch.Tensor):
+            raise TypeError(f"activation_grad's aux must be a tensor; got "
+                            f"{type(activation_grad[1]).__name__}")
+    if activation is not None and activation_grad is not None:
+        raise ValueError("activation and activation_grad exclude each other: "
+                         "one call has one epilogue")
+    if return_aux and activation is None:
+        raise ValueError("return_aux needs an activation")
+    if (activation is not None or activation_grad is not None) \
+            and out_dtype is not torch.bfloat16:
+        raise ValueError("activation and activation_grad need "
+                         "out_dtype=torch.bfloat16")
+    if activation_grad is not None and bias is not None:
+        raise ValueError("activation_grad takes no bias")
+
+
 def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
            xcd_swizzle: bool = False, split_k=None, out_dtype=None,
-           bias: torch.Tensor = None) -> torch.Tensor:
+           bias: torch.Tensor = None, activation=None,
+           return_aux: bool = False, activation_grad=None) -> torch.Tensor:
     """Layout-agnostic front door: returns the logical a [M,K] @ b [K,N].
 
     The layout is read from the strides (matmul_layout: row-major or a
@@ -1099,9 +1290,22 @@ def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
     bias without out_dtype=torch.bfloat16 is a ValueError. split_k works as
     above; a plan of 1 takes the kernel without a split. out_dtype and bias
     are checked with split_k, before any tensor.
+
+    activation="relu" | "gelu" (tanh form; needs out_dtype=torch.bfloat16)
+    applies the activation in the same epilogue: bf16(act(a @ b + bias)),
+    gemm_bf16_act. return_aux=True then returns (y, z), z the bf16
+    pre-activation the GEMM wrote beside y. activation_grad=(name, aux), aux
+    a bf16 [M,N] tensor, returns bf16((a @ b) * act'(aux)) — the backward of
+    the activation folded into the product that forms its incoming gradient;
+    it takes no bias and excludes activation. aux is zero-padded with the
+    output; the padded accumulators are 0, so the cropped result does not
+    change. The three keywords are judged with the ones above, before any
+    tensor; without them this function runs what it ran before them.
     """
     _check_split_k(split_k, ints=True)
     _check_out_dtype_bias(out_dtype, bias)
+    _check_activation_keywords(activation, return_aux, activation_grad,
+                               out_dtype, bias)
     layout, a_st, b_st = matmul_layout(a, b)
     if a.dtype != b.dtype:
         raise TypeError(f"a is {a.dtype}, b is {b.dtype}")
@@ -1131,11 +1335,39 @@ def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
         ap = operand(a_st, *((kp, mp) if a_t else (mp, kp)))
         bp = operand(b_st, *((kp, np_) if b_n else (np_, kp)))
         c = torch.empty(mp, np_, dtype=torch.bfloat16, device=a.device)
-        gemm_bf16_epilogue(c, ap, bp, layout, bias=bias_p, splits=splits,
-                           stream=stream, xcd_swizzle=xcd_swizzle)
-        if (mp, np_) == (m, n):
-            return c
-        return c[:m, :n].contiguous()
+        if activation is None and activation_grad is None:
+            gemm_bf16_epilogue(c, ap, bp, layout, bias=bias_p, splits=splits,
+                               stream=stream, xcd_swizzle=xcd_swizzle)
+            if (mp, np_) == (m, n):
+                return c
+            return c[:m, :n].contiguous()
+
+        def crop(t):
+            return t if (mp, np_) == (m, n) else t[:m, :n].contiguous()
+
+        if activation_grad is not None:
+            name, aux = activation_grad
+            if aux.dtype != torch.bfloat16 or aux.dim() != 2 \
+                    or not aux.is_contiguous():
+                raise TypeError("activation_grad's aux must be a contiguous "
+                                "2-D bfloat16 tensor")
+            if aux.shape != (m, n):
+                raise ValueError(f"activation_grad's aux must have shape "
+                                 f"({m}, {n}); got {tuple(aux.shape)}")
+            if aux.device != a.device:
+                raise TypeError(f"activation_grad's aux is on {aux.device}, "
+                                f"the operands on {a.device}")
+            gemm_bf16_act(c, ap, bp, layout, activation=name,
+                          grad_aux=operand(aux, mp, np_), splits=splits,
+                          stream=stream, xcd_swizzle=xcd_swizzle)
+            return crop(c)
+        z = None
+        if return_aux:
+            z = torch.empty(mp, np_, dtype=torch.bfloat16, device=a.device)
+        gemm_bf16_act(c, ap, bp, layout, activation=activation, bias=bias_p,
+                      aux_out=z, splits=splits, stream=stream,
+                      xcd_swizzle=xcd_swizzle)
+        return (crop(c), crop(z)) if return_aux else crop(c)
     if layout == "nt":
         return matmul_nt(a_st, b_st, stream=stream, xcd_swizzle=xcd_swizzle,
                          split_k=split_k)
@@ -1311,3 +1543,101 @@ def linear_bf16(x: torch.Tensor, w: torch.Tensor, split_k=None,
     if fused is False:
         return _LinearBf16Bias.apply(x, w, bias, split_k)
     return _LinearBf16Fused.apply(x, w, bias, split_k)
+
+
+class _MlpBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, activation, split_k):
+        gelu = activation == "gelu"
+        res = matmul(x, w1.t(), split_k=split_k, out_dtype=torch.bfloat16,
+                     bias=b1, activation=activation, return_aux=gelu)
+        h, z = res if gelu else (res, None)
+        y = matmul(h, w2.t(), split_k=split_k, out_dtype=torch.bfloat16,
+                   bias=b2)
+        # relu: h carries the mask; gelu: the derivative needs z
+        ctx.save_for_backward(x, w1, w2, h, *((z,) if gelu else ()))
+        ctx.activation = activation
+        ctx.split_k = split_k
+        ctx.bias_dtypes = tuple(None if b is None else b.dtype
+                                for b in (b1, b2))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, w2, h = ctx.saved_tensors[:4]
+        aux = ctx.saved_tensors[4] if ctx.activation == "gelu" else h
+        sk = ctx.split_k
+        need = ctx.needs_input_grad
+        bd1, bd2 = ctx.bias_dtypes
+        if not dy.is_contiguous():  # e.g. the expanded scalar of sum()
+            dy = dy.contiguous()
+        dx = dw1 = db1 = dw2 = db2 = None
+        need_b1 = bd1 is not None and need[2]
+        if need[0] or need[1] or need_b1:   # nn: dy [M,O] w2 [O,H]
+            dz = matmul(dy, w2, split_k=sk, out_dtype=torch.bfloat16,
+                        activation_grad=(ctx.activation, aux))
+            if need[0]:                     # nn: dz [M,H] w1 [H,I]
+                dx = matmul(dz, w1, split_k=sk, out_dtype=torch.bfloat16)
+            if need[1]:                     # tn: dz [M,H] x [M,I]
+                dw1 = matmul(dz.t(), x, split_k=sk, out_dtype=torch.bfloat16)
+            if need_b1:
+                db1 = colsum_bf16(dz).to(bd1)
+        if need[3]:                         # tn: dy [M,O] h [M,H]
+            dw2 = matmul(dy.t(), h, split_k=sk, out_dtype=torch.bfloat16)
+        if bd2 is not None and need[4]:
+            db2 = colsum_bf16(dy).to(bd2)
+        return dx, dw1, db1, dw2, db2, None, None
+
+
+def mlp_bf16(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+             w2: torch.Tensor, b2: torch.Tensor, activation: str = "gelu",
+             split_k=None) -> torch.Tensor:
+    """y = act(x @ w1^T + b1) @ w2^T + b2 for bf16 x [M,I], w1 [H,I],
+    w2 [O,H], differentiable; b1 [H] and b2 [O] are bf16, fp32 or None.
+    activation is "relu" or "gelu" (tanh form; the erf form is not built).
+    Every product is a matmul(out_dtype=torch.bfloat16) on the K7 kernels,
+    and the activation and its derivative live in GEMM epilogues
+    (gemm_bf16_act), so no elementwise pass touches the [M,H] tensor:
+
+        forward   h (, z) = matmul(x, w1.t(), bias=b1, activation=...)   nt
+                  y  = matmul(h, w2.t(), bias=b2)                        nt
+        backward  dz  = matmul(dy, w2, activation_grad=(act, aux))       nn
+                  dw2 = matmul(dy.t(), h)                                tn
+                  db2 = colsum_bf16(dy)
+                  dx  = matmul(dz, w1)                                   nn
+                  dw1 = matmul(dz.t(), x)                                tn
+                  db1 = colsum_bf16(dz)
+
+    Saved for the backward pass: x, w1, w2, h and, for gelu, the bf16
+    pre-activation z (aux = z); relu saves no z (aux = h, whose sign is the
+    mask). Only the gradients asked for are computed. split_k is None or
+    "auto", handed to every product (linear_bf16). Shape and dtype rules are
+    linear_bf16's.
+    """
+    _check_split_k(split_k, ints=False)
+    _check_activation_name(activation, "activation")
+    for b, name in ((b1, "b1"), (b2, "b2")):
+        if b is not None and not isinstance(b, torch.Tensor):
+            raise TypeError(f"{name} must be None or a tensor; got "
+                            f"{type(b).__name__}")
+    if x.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 \
+            or x.shape[1] != w1.shape[1] or w1.shape[0] != w2.shape[1]:
+        raise ValueError(f"need x[M,I], w1[H,I], w2[O,H]; got "
+                         f"x{tuple(x.shape)} w1{tuple(w1.shape)} "
+                         f"w2{tuple(w2.shape)}")
+    if x.dtype != torch.bfloat16 or w1.dtype != torch.bfloat16 \
+            or w2.dtype != torch.bfloat16:
+        raise TypeError("x, w1 and w2 must be bf16")
+    if not x.is_contiguous() or not w1.is_contiguous() \
+            or not w2.is_contiguous():
+        raise TypeError("x, w1 and w2 must be contiguous")
+    for b, w, name in ((b1, w1, "b1"), (b2, w2, "b2")):
+        if b is None:
+            continue
+        if b.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"{name} must be bfloat16 or float32, got "
+                            f"{b.dtype}")
+        if b.dim() != 1 or b.shape[0] != w.shape[0]:
+            raise ValueError(f"{name} must have shape ({w.shape[0]},); got "
+                             f"{tuple(b.shape)}")
+    return _MlpBf16.apply(x, w1, b1, w2, b2, activation, split_k)
