@@ -22,7 +22,7 @@ CXXFLAGS   := -O3 -std=c++17 -fPIC --offload-arch=$(GPU_ARCH) -I$(NATIVE) -Wall
 LDEXTRA    ?=
 LDFLAGS    := $(LDEXTRA) -L/opt/rocm/lib -lrocm_smi64 -lrocprofiler-sdk-roctx -lhsa-runtime64
 
-LIB_SRCS   := $(NATIVE)/kernels.hip $(NATIVE)/quant.hip $(NATIVE)/gemm.hip $(NATIVE)/gemm_splitk.hip $(NATIVE)/gemm_layout.hip $(NATIVE)/gemm_layout_splitk.hip $(NATIVE)/gemm_epilogue.hip $(NATIVE)/gemm_act.hip $(NATIVE)/conc.hip $(NATIVE)/topo.hip $(NATIVE)/ipc.hip $(NATIVE)/trace.hip $(NATIVE)/sdma.hip $(NATIVE)/staged.hip $(NATIVE)/step.hip
+LIB_SRCS   := $(NATIVE)/kernels.hip $(NATIVE)/quant.hip $(NATIVE)/gemm.hip $(NATIVE)/gemm_splitk.hip $(NATIVE)/gemm_layout.hip $(NATIVE)/gemm_layout_splitk.hip $(NATIVE)/gemm_epilogue.hip $(NATIVE)/gemm_act.hip $(NATIVE)/gemm_batched.hip $(NATIVE)/conc.hip $(NATIVE)/topo.hip $(NATIVE)/ipc.hip $(NATIVE)/trace.hip $(NATIVE)/sdma.hip $(NATIVE)/staged.hip $(NATIVE)/step.hip
 LIB_OBJS   := $(patsubst $(NATIVE)/%.hip,$(BUILD)/%.o,$(LIB_SRCS))
 
 EXT_SO     := hpc_patterns_amd/_hpk$(EXT_SUFFIX)
@@ -53,8 +53,8 @@ $(BUILD)/%.o: $(NATIVE)/%.hip $(NATIVE)/include/hpk.h | $(BUILD)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 $(BUILD)/sdma.o $(BUILD)/step.o: $(NATIVE)/include/sdma_route.h
-$(BUILD)/gemm.o $(BUILD)/gemm_splitk.o $(BUILD)/gemm_layout.o $(BUILD)/gemm_layout_splitk.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o: $(NATIVE)/include/gemm_device.h
-$(BUILD)/gemm_layout.o $(BUILD)/gemm_layout_splitk.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o: $(NATIVE)/include/gemm_layout_device.h
+$(BUILD)/gemm.o $(BUILD)/gemm_splitk.o $(BUILD)/gemm_layout.o $(BUILD)/gemm_layout_splitk.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o $(BUILD)/gemm_batched.o: $(NATIVE)/include/gemm_device.h
+$(BUILD)/gemm_layout.o $(BUILD)/gemm_layout_splitk.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o $(BUILD)/gemm_batched.o: $(NATIVE)/include/gemm_layout_device.h
 $(BUILD)/step.o: $(NATIVE)/include/push_pool.h
 
 $(BUILD)/ext.o: $(NATIVE)/ext.cpp $(NATIVE)/include/hpk.h | $(BUILD)

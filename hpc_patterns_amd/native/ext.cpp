@@ -218,6 +218,32 @@ PYBIND11_MODULE(_hpk, m) {
         py::arg("stream") = 0, py::arg("xcd_swizzle") = 0,
         "C bf16 = bf16(op(A) @ op(B) + bias[n]); layout nt | nn | tn | tt, "
         "bias 0 = none; workspace [splits][M][N] fp32 when splits > 1");
+  m.def("gemm_bf16_batched",
+        [](uintptr_t c, int c_is_bf16, uintptr_t a, uintptr_t b, long m,
+           long n, long k, long batch, long lda, long bsa, long ldb, long bsb,
+           long ldc, long bsc, const std::string& layout, float alpha,
+           uintptr_t stream, int xcd_swizzle) {
+          hpk::launch_gemm_bf16_batched(
+              reinterpret_cast<void*>(c), c_is_bf16,
+              reinterpret_cast<const void*>(a),
+              reinterpret_cast<const void*>(b), m, n, k, batch, lda, bsa, ldb,
+              bsb, ldc, bsc, layout.c_str(), alpha, as_stream(stream),
+              xcd_swizzle);
+        },
+        py::arg("c"), py::arg("c_is_bf16"), py::arg("a"), py::arg("b"),
+        py::arg("m"), py::arg("n"), py::arg("k"), py::arg("batch"),
+        py::arg("lda"), py::arg("bsa"), py::arg("ldb"), py::arg("bsb"),
+        py::arg("ldc"), py::arg("bsc"), py::arg("layout"),
+        py::arg("alpha") = 1.0f, py::arg("stream") = 0,
+        py::arg("xcd_swizzle") = 0,
+        "C_b = alpha * op(A_b) @ op(B_b), b < batch; layout nt | nn | tn | "
+        "tt; ld = row stride, bs = batch stride, in elements");
+  m.def("gemm_batched_c_disjoint", &hpk::gemm_batched_c_disjoint,
+        py::arg("batch"), py::arg("m"), py::arg("n"), py::arg("ldc"),
+        py::arg("bsc"),
+        "ldc >= n and the batches' C images pairwise disjoint (batch-major "
+        "or interleaved inside a row); the function the launcher calls");
+  m.attr("GEMM_BATCHED_MAX_BATCH") = hpk::kGemmBatchedMaxBatch;
   m.def("gemm_bf16_act",
         [](uintptr_t c, uintptr_t aux, uintptr_t a, uintptr_t b,
            uintptr_t bias, long m, long n, long k, const std::string& layout,

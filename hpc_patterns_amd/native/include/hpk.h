@@ -271,6 +271,46 @@ void launch_gemm_bf16_act(void* C, void* aux, const void* A, const void* B,
                           void* workspace, hipStream_t stream,
                           int xcd_swizzle = 0);
 
+// Batched and strided operands (gemm_batched.hip): C_b[M,N] = alpha *
+// op(A_b) @ op(B_b) for b = 0 .. batch-1, bf16 operands in layout nt | nn |
+// tn | tt as stored (as above), C fp32 or bf16 (c_is_bf16). Each of A, B, C
+// has a row stride ld and a batch stride bs, both in elements: a
+// K-contiguous operand is read at P + b*bs + row*ld + k, an operand stored
+// [K, X] at P + b*bs + k*ld + x, C_b[i][j] is written at C + b*bsC + i*ldc
+// + j. The grid is (tiles, batch). The bodies are k_gemm_bf16_nt_db<2,4>
+// and k_gemm_bf16_lay, so with alpha == 1 an fp32 C holds their bits; the
+// epilogue is one fp32 multiply by alpha (always executed) and, for a bf16
+// C, one round-to-nearest-even conversion behind it and the staged
+// whole-row store of launch_gemm_bf16_epilogue. No bias, activation or
+// split-K. Contract: docs/gemm.md, "Batched and strided operands". Throws
+// std::invalid_argument on an unknown layout, std::runtime_error unless
+//   M,N % 128 == 0, K % 64 == 0, 1 <= batch <= kGemmBatchedMaxBatch;
+//   A and B on 16-byte boundaries, lda, ldb, bsA, bsB % 8 == 0, lda and ldb
+//   at least the stored row length, bsA, bsB >= 0 (0 broadcasts the
+//   operand);
+//   gemm_batched_c_disjoint(batch, M, N, ldc, bsC);
+//   a bf16 C on a 16-byte boundary with ldc, bsC % 8 == 0.
+// With batch == 1 the three batch strides are ignored.
+constexpr long kGemmBatchedMaxBatch = 65535; // gridDim.y
+// ldc >= N and the batches' C images pairwise disjoint, in one of the two
+// forms the launcher takes: batch-major (an image ends before the next
+// begins) or interleaved inside a row (the batches are column blocks of one
+// wide row). Pure host function; tests/test_gemm_batched_logic.py checks it
+// against the enumerated address sets.
+inline bool gemm_batched_c_disjoint(long batch, long M, long N, long ldc,
+                                    long bsC) {
+  if (batch < 1 || M < 1 || N < 1 || ldc < N) return false;
+  if (batch == 1) return true;
+  if (bsC >= (M - 1) * ldc + N) return true;
+  return bsC >= N && ldc >= (batch - 1) * bsC + N;
+}
+void launch_gemm_bf16_batched(void* C, int c_is_bf16, const void* A,
+                              const void* B, long M, long N, long K,
+                              long batch, long lda, long bsA, long ldb,
+                              long bsB, long ldc, long bsC, const char* layout,
+                              float alpha, hipStream_t stream,
+                              int xcd_swizzle = 0);
+
 // Column sums of a bf16 matrix (gemm_epilogue.hip): out[n] = sum_m x[m,n],
 // the bias gradient of a linear layer. x [M,N] bf16 contiguous, N % 8 == 0,
 // 16-byte aligned; out fp32. Row chunk r of R sums rows colsum_rows(M, R, r)

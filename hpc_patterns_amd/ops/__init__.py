@@ -1641,3 +1641,291 @@ def mlp_bf16(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
             raise ValueError(f"{name} must have shape ({w.shape[0]},); got "
                              f"{tuple(b.shape)}")
     return _MlpBf16.apply(x, w1, b1, w2, b2, activation, split_k)
+
+
+# ---------------------------------------------------------------------------
+# Batched and strided operands (native/gemm_batched.hip)
+# ---------------------------------------------------------------------------
+
+_BATCHED_LAYOUTS = {"nt": (False, False), **_LAYOUTS}
+GEMM_BATCHED_MAX_BATCH = 65535      # gridDim.y
+
+
+def gemm_batched_c_disjoint(batch: int, m: int, n: int, ldc: int,
+                            bsc: int) -> bool:
+    """ldc >= n and the C images of the batches pairwise disjoint, in one of
+    the two forms gemm_bf16_batched takes: batch-major, bsc >= (m-1)*ldc + n
+    (an image ends before the next begins), or interleaved inside a row,
+    bsc >= n and ldc >= (batch-1)*bsc + n (the batches are column blocks of
+    one wide row). With batch == 1 bsc is ignored. Pure arithmetic — the
+    launcher's own rule (native gemm_batched_c_disjoint)."""
+    if batch < 1 or m < 1 or n < 1 or ldc < n:
+        return False
+    if batch == 1:
+        return True
+    if bsc >= (m - 1) * ldc + n:
+        return True
+    return bsc >= n and ldc >= (batch - 1) * bsc + n
+
+
+def _check_alpha(alpha):
+    """alpha of bmm / bmm_bf16, on its type alone: a real number, finite or
+    not, never a tensor"""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)):
+        raise TypeError(f"alpha must be a real number (int or float), not "
+                        f"{type(alpha).__name__}")
+
+
+def gemm_bf16_batched(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                      layout: str = "nt", alpha: float = 1.0, stream=None,
+                      xcd_swizzle: bool = False) -> None:
+    """K7 batched: C_i[M,N] = alpha * op(A_i) @ op(B_i) for every i of the
+    leading dimension, on 3-D bf16 operands AS STORED and read in place
+    through their strides (native/gemm_batched.hip).
+
+        layout  a          b
+        "nt"    [B,M,K]    [B,N,K]
+        "nn"    [B,M,K]    [B,K,N]
+        "tn"    [B,K,M]    [B,K,N]
+        "tt"    [B,K,M]    [B,N,K]
+
+    c is [B,M,N], fp32 or bf16; its dtype picks the kernel. Every tensor
+    needs stride(2) == 1; stride(1) is its row stride ld and stride(0) its
+    batch stride bs, in elements, taken from the tensor — a head of a
+    [tokens, heads*dim] activation is a, b or c with ld = heads*dim and
+    bs = dim. bs may be 0 for a or b (an expand()ed operand: one matrix for
+    every batch). Requires M,N % 128 == 0, K % 64 == 0, B <= 65535; a and b
+    on 16-byte boundaries with ld and bs multiples of 8; the C images
+    pairwise disjoint (gemm_batched_c_disjoint); a bf16 c also on a 16-byte
+    boundary with ld and bs multiples of 8 (bmm pads and copies where
+    needed). With B == 1 the batch strides mean nothing and are not judged.
+
+    With alpha == 1 an fp32 c holds the bits of gemm_bf16_layout (nt: of
+    gemm_bf16 under HPK_GEMM_VARIANT=db) per batch. alpha is one fp32
+    multiply on the accumulator, always executed; a bf16 c is rounded once,
+    to nearest even, after it. No bias, activation or split-K.
+    """
+    if layout not in _BATCHED_LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}; expected one of "
+                         f"'nt', 'nn', 'tn', 'tt'")
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+        if a.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8) \
+                or b.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8):
+            raise TypeError("only bf16 has the batched, strided GEMM: the "
+                            "8-bit and 4-bit transposed LDS reads "
+                            "(ds_read_b64_tr_b8 / _tr_b4) are not built here")
+        raise TypeError("a and b must be bf16; c fp32 or bf16")
+    if c.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("a and b must be bf16; c fp32 or bf16")
+    _check_alpha(alpha)
+    for t, name in ((c, "c"), (a, "a"), (b, "b")):
+        if not t.is_cuda or t.dim() != 3 or t.stride(2) != 1:
+            raise TypeError(f"{name} must be a 3-D CUDA tensor with "
+                            f"stride(2) == 1; got shape {tuple(t.shape)}, "
+                            f"strides {t.stride()}")
+    if a.device != c.device or b.device != c.device:
+        raise TypeError("a, b and c must be on one device")
+    a_t, b_n = _BATCHED_LAYOUTS[layout]
+    batch = c.shape[0]
+    k, m = a.shape[1:] if a_t else a.shape[:0:-1]
+    kb, n = b.shape[1:] if b_n else b.shape[:0:-1]
+    if kb != k or tuple(c.shape[1:]) != (m, n) or a.shape[0] != batch \
+            or b.shape[0] != batch:
+        raise ValueError(f"shape mismatch for layout {layout}: "
+                         f"A{tuple(a.shape)} B{tuple(b.shape)} "
+                         f"C{tuple(c.shape)}")
+    if not 1 <= batch <= GEMM_BATCHED_MAX_BATCH:
+        raise ValueError(f"gemm_bf16_batched requires 1 <= batch <= "
+                         f"{GEMM_BATCHED_MAX_BATCH}; got {batch}")
+    if m < 128 or n < 128 or k < 64 or m % 128 or n % 128 or k % 64:
+        raise ValueError(f"gemm_bf16_batched requires M,N % 128 == 0 and "
+                         f"K % 64 == 0; got M={m} N={n} K={k}")
+    if a.data_ptr() % 16 != 0 or b.data_ptr() % 16 != 0:
+        raise ValueError("a and b must start on 16-byte boundaries (they "
+                         "are fetched in 16-byte chunks)")
+
+    def strides(t):
+        return t.stride(1), (t.stride(0) if batch > 1 else 0)
+
+    (lda, bsa), (ldb, bsb), (ldc, bsc) = strides(a), strides(b), strides(c)
+    for name, ld, bs, row in (("a", lda, bsa, a.shape[2]),
+                              ("b", ldb, bsb, b.shape[2])):
+        if ld % 8 or bs % 8:
+            raise ValueError(f"{name}: stride(1) = {ld} and stride(0) = {bs} "
+                             f"must be multiples of 8 elements (every "
+                             f"16-byte chunk stays aligned)")
+        if ld < row:
+            raise ValueError(f"{name}: stride(1) = {ld} is below its row "
+                             f"length {row}")
+    if not gemm_batched_c_disjoint(batch, m, n, ldc, bsc):
+        raise ValueError(f"c's batches overlap or its rows do: stride(1) = "
+                         f"{ldc}, stride(0) = {bsc} for {batch} x {m} x {n}; "
+                         f"need stride(1) >= N and either stride(0) >= "
+                         f"(M-1)*stride(1) + N or stride(0) >= N and "
+                         f"stride(1) >= (B-1)*stride(0) + N")
+    if c.dtype == torch.bfloat16 and (c.data_ptr() % 16 or ldc % 8
+                                      or bsc % 8):
+        raise ValueError("a bf16 c must start on a 16-byte boundary with "
+                         "stride(1) and stride(0) multiples of 8 elements "
+                         "(its rows are written as 16-byte stores)")
+    native().gemm_bf16_batched(
+        c.data_ptr(), int(c.dtype == torch.bfloat16), a.data_ptr(),
+        b.data_ptr(), m, n, k, batch, lda, bsa, ldb, bsb, ldc, bsc, layout,
+        float(alpha), _stream_handle(stream), int(xcd_swizzle))
+
+
+def bmm_layout(a: torch.Tensor, b: torch.Tensor):
+    """(layout, a_stored, b_stored) of the logical batched product
+    a [B,M,K] @ b [B,K,N], read from the strides; pure tensor metadata, any
+    device.
+
+    An argument is "n" if its stride(2) == 1 — asked first, so a tensor with
+    a size-1 dimension, whose strides fit both readings, counts as row-major
+    as in matmul_layout — and its stored tensor is itself; otherwise "t" if
+    its stride(1) == 1, stored as transpose(1, 2) (a view, never a copy).
+    The other strides are free: an expand()ed batch (stride(0) == 0) and a
+    head of an interleaved activation (permute) are both fine. Anything
+    else raises TypeError: no hidden copy.
+    """
+    def stored(t, name):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise TypeError(f"{name} must be a 3-D tensor")
+        if t.stride(2) == 1:
+            return t, "n"
+        if t.stride(1) == 1:
+            return t.transpose(1, 2), "t"
+        raise TypeError(f"{name} has no unit stride in its last two "
+                        f"dimensions (shape {tuple(t.shape)}, strides "
+                        f"{t.stride()}); bmm makes no hidden copies")
+    a_st, fa = stored(a, "a")
+    b_st, fb = stored(b, "b")
+    if a.shape[0] != b.shape[0] or a.shape[2] != b.shape[1]:
+        raise ValueError(f"need a[B,M,K] @ b[B,K,N]; got a{tuple(a.shape)} "
+                         f"b{tuple(b.shape)}")
+    return fa + fb, a_st, b_st
+
+
+def bmm_direct(t: torch.Tensor, row_mult: int, col_mult: int) -> bool:
+    """Whether bmm hands the stored operand t [B,R,C] to the kernel as it
+    is (True) or makes a zero-padded contiguous copy (False): whole tiles
+    (R % row_mult == 0, C % col_mult == 0; 128 along M or N, 64 along K), a
+    unit last stride, stride(1) and — for B > 1 — stride(0) multiples of 8,
+    stride(1) no shorter than a row, and a start on a 16-byte boundary.
+    Pure metadata, any device."""
+    batch, rows, cols = t.shape
+    if rows == 0 or cols == 0 or rows % row_mult or cols % col_mult:
+        return False
+    if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < cols:
+        return False
+    if batch > 1 and t.stride(0) % 8:
+        return False
+    return t.data_ptr() % 16 == 0
+
+
+def _bmm_operand(t: torch.Tensor, rows: int, cols: int, row_mult: int,
+                 col_mult: int):
+    """t as the kernel takes it: itself, or a zero-padded contiguous copy
+    [B, rows, cols]; a broadcast operand (stride(0) == 0) is padded once and
+    expanded again"""
+    if bmm_direct(t, row_mult, col_mult):
+        return t
+    batch = t.shape[0]
+    once = batch > 1 and t.stride(0) == 0
+    out = torch.zeros(1 if once else batch, rows, cols, dtype=t.dtype,
+                      device=t.device)
+    out[:, : t.shape[1], : t.shape[2]] = t[:1] if once else t
+    return out.expand(batch, rows, cols) if once else out
+
+
+def bmm(a: torch.Tensor, b: torch.Tensor, out_dtype=None, alpha=1.0,
+        stream=None) -> torch.Tensor:
+    """Batched front door: alpha * (a [B,M,K] @ b [B,K,N]) for bf16 a, b of
+    any B, M, N, K, as a fresh contiguous [B,M,N] tensor — fp32, or bf16
+    for out_dtype=torch.bfloat16 (rounded once, after the multiply).
+
+    The layout is read from the strides (bmm_layout: no hidden copy of a
+    tensor with no unit stride, that is a TypeError). A stored operand of
+    whole tiles with qualifying strides and alignment (bmm_direct) goes to
+    gemm_bf16_batched as it is — for x, y [T, H*D] with T, D % 128 == 0,
+
+        q = x.view(T, H, D).permute(1, 0, 2)
+        k = y.view(T, H, D).permute(1, 2, 0)
+        s = bmm(q, k, alpha=D ** -0.5)
+
+    is layout nt with ld = H*D, bs = D and copies nothing. Everything else
+    is copied zero-padded to gemm_layout_pad_shapes (zeros add nothing) and
+    the result is sliced, as matmul does; a broadcast operand is padded
+    once, not B times. More than 65535 batches run as several launches.
+    out_dtype and alpha (a real number, finite or not, never a tensor) are
+    judged before any tensor is looked at.
+    """
+    if out_dtype is not None and out_dtype is not torch.bfloat16:
+        raise ValueError(f"out_dtype must be None or torch.bfloat16; got "
+                         f"{out_dtype!r}")
+    _check_alpha(alpha)
+    layout, a_st, b_st = bmm_layout(a, b)
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+        if a.dtype in (torch.float8_e4m3fn, torch.int8, torch.uint8):
+            raise TypeError(_NO_NARROW_TR)
+        raise TypeError(f"bmm takes bf16 operands; got {a.dtype} and "
+                        f"{b.dtype}")
+    if a.device != b.device:
+        raise TypeError(f"a is on {a.device}, b on {b.device}")
+    batch, m, k = a.shape
+    n = b.shape[2]
+    dtype = torch.float32 if out_dtype is None else torch.bfloat16
+    if batch == 0 or m == 0 or n == 0 or k == 0:
+        return torch.zeros(batch, m, n, dtype=dtype, device=a.device)
+    mp, np_, kp = gemm_layout_pad_shapes(m, n, k)
+    a_t, b_n = _BATCHED_LAYOUTS[layout]
+    ap = _bmm_operand(a_st, *((kp, mp, 64, 128) if a_t else (mp, kp, 128, 64)))
+    bp = _bmm_operand(b_st, *((kp, np_, 64, 128) if b_n
+                              else (np_, kp, 128, 64)))
+    c = torch.empty(batch, mp, np_, dtype=dtype, device=a.device)
+    for b0 in range(0, batch, GEMM_BATCHED_MAX_BATCH):
+        b1 = min(batch, b0 + GEMM_BATCHED_MAX_BATCH)
+        gemm_bf16_batched(c[b0:b1], ap[b0:b1], bp[b0:b1], layout,
+                          alpha=alpha, stream=stream)
+    if (mp, np_) == (m, n):
+        return c
+    return c[:, :m, :n].contiguous()
+
+
+class _BmmBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, alpha):
+        ctx.save_for_backward(a, b)
+        ctx.alpha = alpha
+        return bmm(a, b, out_dtype=torch.bfloat16, alpha=alpha)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, b = ctx.saved_tensors
+        if dy.stride(2) != 1 and dy.stride(1) != 1:
+            dy = dy.contiguous()    # e.g. the expanded scalar of sum()
+        da = db = None
+        if ctx.needs_input_grad[0]:     # [B,M,N] @ [B,N,K]
+            da = bmm(dy, b.transpose(1, 2), out_dtype=torch.bfloat16,
+                     alpha=ctx.alpha)
+        if ctx.needs_input_grad[1]:     # [B,K,M] @ [B,M,N]
+            db = bmm(a.transpose(1, 2), dy, out_dtype=torch.bfloat16,
+                     alpha=ctx.alpha)
+        return da, db, None
+
+
+def bmm_bf16(a: torch.Tensor, b: torch.Tensor, alpha=1.0) -> torch.Tensor:
+    """y = alpha * (a [B,M,K] @ b [B,K,N]) for bf16 a and b, differentiable;
+    every product is a bmm(out_dtype=torch.bfloat16) on the batched K7
+    kernels, fp32 accumulation, one rounding, and nothing is transposed in
+    memory — the layouts come from the strides:
+
+        forward   y  = bmm(a, b, alpha)
+        backward  da = bmm(dy, b.transpose(1, 2), alpha)
+                  db = bmm(a.transpose(1, 2), dy, alpha)
+
+    Only the gradients asked for are computed. a and b are what bmm takes:
+    heads of an interleaved activation and expand()ed operands included
+    (autograd sums the gradient of an expand itself).
+    """
+    _check_alpha(alpha)
+    return _BmmBf16.apply(a, b, alpha)
