@@ -54,7 +54,8 @@ $(BUILD)/%.o: $(NATIVE)/%.hip $(NATIVE)/include/hpk.h | $(BUILD)
 
 $(BUILD)/sdma.o $(BUILD)/step.o: $(NATIVE)/include/sdma_route.h
 $(BUILD)/gemm.o $(BUILD)/gemm_splitk.o $(BUILD)/gemm_layout.o $(BUILD)/gemm_layout_splitk.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o $(BUILD)/gemm_batched.o: $(NATIVE)/include/gemm_device.h
-$(BUILD)/gemm_layout.o $(BUILD)/gemm_layout_splitk.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o $(BUILD)/gemm_batched.o: $(NATIVE)/include/gemm_layout_device.h
+$(BUILD)/gemm_layout.o $(BUILD)/gemm_layout_splitk.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o $(BUILD)/gemm_batched.o: $(NATIVE)/include/gemm_layout_device.h $(NATIVE)/include/gemm_host.h $(NATIVE)/include/gemm_bf16_lay_loop.inc
+$(BUILD)/gemm.o $(BUILD)/gemm_epilogue.o $(BUILD)/gemm_act.o: $(NATIVE)/include/gemm_bf16_nt_loop.inc
 $(BUILD)/step.o: $(NATIVE)/include/push_pool.h
 
 $(BUILD)/ext.o: $(NATIVE)/ext.cpp $(NATIVE)/include/hpk.h | $(BUILD)

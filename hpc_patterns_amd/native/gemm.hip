@@ -166,6 +166,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_bf16_nt(
 // for tile t (FIFO per wave, so `s_waitcnt vmcnt(8)` retires exactly
 // tile t's 8 DMAs while t+1's stay in flight), and the barriers are raw
 // s_barrier + lgkmcnt(0) so nothing re-drains the queue. 64 KiB LDS.
+// The loop is include/gemm_bf16_nt_loop.inc, which the bf16-output and
+// activation NT kernels (gemm_epilogue.hip, gemm_act.hip) include as well.
 template <int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_bf16_nt_db(
     float* __restrict__ C, const __hip_bfloat16* __restrict__ A,
@@ -191,57 +193,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_gemm_bf16_nt_db(
   constexpr int ISSUES = TILE_HALF / (THREADS * 8);
   f32x4 acc[MREP][NREP] = {};
 
-  auto stage = [&](int buf, int k0) {
-    __hip_bfloat16* dst = lds + (long)buf * 2 * TILE_HALF;
-    for (int issue = 0; issue < ISSUES; ++issue) {
-      long o_base = (long)issue * elems_per_issue + (long)wid * (64 * 8);
-      long o = lds_unskew(o_base + (long)lane * 8);
-      int row = (int)(o / BK);
-      int kk = (int)(o % BK);
-      const __hip_bfloat16* ga = A + (brow + row) * (long)K + k0 + kk;
-      const __hip_bfloat16* gb = B + (bcol + row) * (long)K + k0 + kk;
-      glds16(ga, dst + o_base);
-      glds16(gb, dst + TILE_HALF + o_base);
-    }
-  };
-
-  stage(0, 0);
-  for (int k0 = 0; k0 < K; k0 += BK) {
-    const int cur = (k0 / BK) & 1;
-    const bool more = (k0 + BK) < K;
-    if (more) stage(cur ^ 1, k0 + BK); // next tile's DMA, other buffer
-    // retire exactly the CURRENT tile's DMAs (2*ISSUES per thread issued
-    // first; FIFO), leaving the prefetch in flight across the barrier
-    if (more)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ISSUES) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier(); // current buffer complete for all waves
-
-    const __hip_bfloat16* la = lds + (long)cur * 2 * TILE_HALF;
-    const __hip_bfloat16* lb = la + TILE_HALF;
-    for (int kk = 0; kk < BK; kk += 32) {
-      const int kfrag = kk + 8 * (lane >> 4);
-      bf16x8 afrag[MREP], bfrag[NREP];
-      for (int m = 0; m < MREP; ++m) {
-        int row = wr * WTM + m * 16 + (lane & 15);
-        afrag[m] = *(const bf16x8*)(la + lds_skew(row * BK + kfrag));
-      }
-      for (int n = 0; n < NREP; ++n) {
-        int col = wc * WTN + n * 16 + (lane & 15);
-        bfrag[n] = *(const bf16x8*)(lb + lds_skew(col * BK + kfrag));
-      }
-      for (int m = 0; m < MREP; ++m)
-        for (int n = 0; n < NREP; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[m], bfrag[n], acc[m][n], 0, 0, 0);
-    }
-    // every wave done READING buf[cur] before the next iteration's
-    // prefetch overwrites it
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
+#include "include/gemm_bf16_nt_loop.inc"
 
   for (int m = 0; m < MREP; ++m)
     for (int n = 0; n < NREP; ++n) {

@@ -8,12 +8,12 @@
 //             that forms dy W2
 //
 // for act = relu | gelu (tanh form). k_gemm_bf16_nt_act and
-// k_gemm_bf16_lay_act<A_T, B_N> are the bodies of k_gemm_bf16_nt_out and
-// k_gemm_bf16_lay_out (gemm_epilogue.hip), pasted: staging, the counted
-// vmcnt / lgkmcnt, the raw barriers, the hpk_tile_id preamble and the MFMA
-// operand order are theirs, so the accumulators are theirs bit for bit.
-// They are kernels of their own, not a switch inside the parents
-// (docs/findings.md #28).
+// k_gemm_bf16_lay_act<A_T, B_N> run the K loops of k_gemm_bf16_nt_out and
+// k_gemm_bf16_lay_out (gemm_epilogue.hip): include/gemm_bf16_nt_loop.inc
+// and include/gemm_bf16_lay_loop.inc hold the one copy of each — staging,
+// the counted vmcnt / lgkmcnt, the raw barriers, the MFMA operand order —
+// so the accumulators are theirs bit for bit. They are kernels of their
+// own, not a switch inside the parents (docs/findings.md #28).
 //
 // Forward epilogue: the Y tile goes through the staged image of
 // gemm_epilogue.hip (gemm_out_lds_offset / gemm_out_read, include/hpk.h) in
@@ -45,6 +45,7 @@
 
 #include "include/hpk.h"
 #include "include/gemm_device.h"
+#include "include/gemm_host.h"
 #include "include/gemm_layout_device.h"
 
 #include <hip/hip_bf16.h>
@@ -57,25 +58,7 @@
 namespace hpk {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef unsigned __attribute__((may_alias)) lds_u32;
-typedef u32x4 __attribute__((may_alias)) lds_u32x4;
-
 constexpr int kImgBytes = BM * BN * 2; // one staged bf16 tile: 32 KiB
-
-// bf16(lo) | bf16(hi) << 16, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf16_lo(unsigned d) {
-  return __builtin_bit_cast(float, d << 16);
-}
-__device__ __forceinline__ float bf16_hi(unsigned d) {
-  return __builtin_bit_cast(float, d & 0xffff0000u);
-}
 
 // constants of the tanh GELU, rounded once from double
 constexpr double kSqrt2OverPi = 0.7978845608028654;
@@ -112,36 +95,6 @@ __device__ __forceinline__ float act_grad(float z) {
   const float ss = ER * R; // s (1 - s)
   const float m = (z * kGeluC2) * __builtin_fmaf(z * z, kGeluC3, 1.f);
   return __builtin_fmaf(m, ss, s);
-}
-
-// The store loop of store_tile_bf16 (gemm_epilogue.hip): the staged image at
-// `img` to the tile of `dst` at (brow, bcol), 2 passes x 512 threads x
-// (2 rows x 8 columns). Behind the barrier that completes the image.
-__device__ __forceinline__ void flush_tile(__hip_bfloat16* __restrict__ dst,
-                                           const char* img, long brow,
-                                           long bcol, int N, int tid) {
-  for (int p = 0; p < 2; ++p) {
-    const GemmOutRead r0 = gemm_out_read(tid, p, 0);
-    const GemmOutRead r1 = gemm_out_read(tid, p, 1);
-    const u32x4 q0 =
-        *(const lds_u32x4*)(img + gemm_out_lds_offset(r0.row, r0.col));
-    const u32x4 q1 =
-        *(const lds_u32x4*)(img + gemm_out_lds_offset(r1.row, r1.col));
-    const bool odd_first = (tid >> 3) & 1;
-    const u32x4 ev = odd_first ? q1 : q0; // columns 8j .. 8j+3, both rows
-    const u32x4 od = odd_first ? q0 : q1; // columns 8j+4 .. 8j+7
-    const u32x4 top = {(ev[0] & 0xffffu) | (ev[1] << 16),
-                       (ev[2] & 0xffffu) | (ev[3] << 16),
-                       (od[0] & 0xffffu) | (od[1] << 16),
-                       (od[2] & 0xffffu) | (od[3] << 16)};
-    const u32x4 bot = {(ev[0] >> 16) | (ev[1] & 0xffff0000u),
-                       (ev[2] >> 16) | (ev[3] & 0xffff0000u),
-                       (od[0] >> 16) | (od[1] & 0xffff0000u),
-                       (od[2] >> 16) | (od[3] & 0xffff0000u)};
-    __hip_bfloat16* d = dst + (brow + r0.row) * (long)N + bcol + 8 * (tid & 15);
-    *(u32x4*)d = top;
-    *(u32x4*)(d + N) = bot;
-  }
 }
 
 // Forward epilogue of both GEMM kernels: acc is the 64x32 sub-tile of wave
@@ -247,9 +200,10 @@ __device__ __forceinline__ void act_epilogue(
                              wc);
 }
 
-// The body of k_gemm_bf16_nt_out (gemm_epilogue.hip): 8 waves as 2(M) x
-// 4(N), 64x32 per wave, 2 buffers x (A|B) tile = 64 KiB LDS. aux: forward,
-// where Z goes (nullptr: not written); gradient, the tensor act' is taken of.
+// k_gemm_bf16_nt_out (gemm_epilogue.hip) with the activation epilogues: 8
+// waves as 2(M) x 4(N), 64x32 per wave, 2 buffers x (A|B) tile = 64 KiB
+// LDS. aux: forward, where Z goes (nullptr: not written); gradient, the
+// tensor act' is taken of.
 template <int ACT, int MODE>
 __global__ __launch_bounds__(512) void k_gemm_bf16_nt_act(
     __hip_bfloat16* __restrict__ C, __hip_bfloat16* __restrict__ aux,
@@ -278,65 +232,14 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_nt_act(
   constexpr int ISSUES = TILE_HALF / (THREADS * 8);
   f32x4 acc[MREP][NREP] = {};
 
-  auto stage = [&](int buf, int k0) {
-    __hip_bfloat16* dst = lds + (long)buf * 2 * TILE_HALF;
-    for (int issue = 0; issue < ISSUES; ++issue) {
-      long o_base = (long)issue * elems_per_issue + (long)wid * (64 * 8);
-      long o = lds_unskew(o_base + (long)lane * 8);
-      int row = (int)(o / BK);
-      int kk = (int)(o % BK);
-      const __hip_bfloat16* ga = A + (brow + row) * (long)K + k0 + kk;
-      const __hip_bfloat16* gb = B + (bcol + row) * (long)K + k0 + kk;
-      glds16(ga, dst + o_base);
-      glds16(gb, dst + TILE_HALF + o_base);
-    }
-  };
-
-  stage(0, 0);
-  for (int k0 = 0; k0 < K; k0 += BK) {
-    const int cur = (k0 / BK) & 1;
-    const bool more = (k0 + BK) < K;
-    if (more) stage(cur ^ 1, k0 + BK); // next tile's DMA, other buffer
-    // retire exactly the CURRENT tile's DMAs (2*ISSUES per thread issued
-    // first; FIFO), leaving the prefetch in flight across the barrier
-    if (more)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ISSUES) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier(); // current buffer complete for all waves
-
-    const __hip_bfloat16* la = lds + (long)cur * 2 * TILE_HALF;
-    const __hip_bfloat16* lb = la + TILE_HALF;
-    for (int kk = 0; kk < BK; kk += 32) {
-      const int kfrag = kk + 8 * (lane >> 4);
-      bf16x8 afrag[MREP], bfrag[NREP];
-      for (int m = 0; m < MREP; ++m) {
-        int row = wr * WTM + m * 16 + (lane & 15);
-        afrag[m] = *(const bf16x8*)(la + lds_skew(row * BK + kfrag));
-      }
-      for (int n = 0; n < NREP; ++n) {
-        int col = wc * WTN + n * 16 + (lane & 15);
-        bfrag[n] = *(const bf16x8*)(lb + lds_skew(col * BK + kfrag));
-      }
-      for (int m = 0; m < MREP; ++m)
-        for (int n = 0; n < NREP; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[m], bfrag[n], acc[m][n], 0, 0, 0);
-    }
-    // every wave done READING buf[cur] before the next iteration's
-    // prefetch overwrites it — and, behind the last tile, before the
-    // epilogue's images do
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
+#include "include/gemm_bf16_nt_loop.inc"
 
   act_epilogue<ACT, MODE>(C, aux, bias, acc, lds, brow, bcol, N, tid, lane,
                           wr, wc);
 }
 
-// The body of k_gemm_bf16_lay_out (gemm_epilogue.hip). A_T: A is stored
-// [K,M]; B_N: B is stored [K,N].
+// k_gemm_bf16_lay_out (gemm_epilogue.hip) with the activation epilogues.
+// A_T: A is stored [K,M]; B_N: B is stored [K,N].
 template <bool A_T, bool B_N, int ACT, int MODE>
 __global__ __launch_bounds__(512) void k_gemm_bf16_lay_act(
     __hip_bfloat16* __restrict__ C, __hip_bfloat16* __restrict__ aux,
@@ -362,94 +265,14 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_lay_act(
   constexpr int ISSUES = TILE_HALF / (THREADS * 8);
   f32x4 acc[MREP][NREP] = {};
 
-  // lane-linear LDS write; the image is in the global chunk each lane takes
-  auto stage = [&](int buf, long k0) {
-    In* dst = lds + (long)buf * 2 * TILE_HALF;
-    for (int issue = 0; issue < ISSUES; ++issue) {
-      long o_base = (long)issue * elems_per_issue + (long)wid * (64 * 8);
-      // K-contiguous: [128 rows][64 k], skewed
-      long o = lds_unskew(o_base + (long)lane * 8);
-      int row = (int)(o / BK);
-      int kk = (int)(o % BK);
-      // X-contiguous: [64 k-rows][128 x]; slot = 16-byte chunk index
-      int slot = (int)(o_base / 8) + lane;
-      int krow = slot >> 4;
-      int x = 8 * ((slot & 15) ^ lay_key(krow));
-      const In* ga = A_T ? A + (k0 + krow) * (long)M + brow + x
-                         : A + (brow + row) * (long)K + k0 + kk;
-      const In* gb = B_N ? B + (k0 + krow) * (long)N + bcol + x
-                         : B + (bcol + row) * (long)K + k0 + kk;
-      glds16(ga, dst + o_base);
-      glds16(gb, dst + TILE_HALF + o_base);
-    }
-  };
-
-  stage(0, 0);
-  const int trips = K / BK;
-  for (int t = 0; t < trips; ++t) {
-    const int cur = t & 1;
-    const bool more = t + 1 < trips;
-    if (more) stage(cur ^ 1, (long)(t + 1) * BK);
-    // retire exactly the CURRENT tile's DMAs (2*ISSUES per thread, issued
-    // first; FIFO), leaving the prefetch in flight across the barrier
-    if (more)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ISSUES) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier(); // current buffer complete for all waves
-
-    const In* la = lds + (long)cur * 2 * TILE_HALF;
-    const In* lb = la + TILE_HALF;
-    // both k-steps' transposed reads are started at once; step 0 waits
-    // for all but step 1's (TR_STEP of them, the most recent), step 1
-    // for the rest
-    constexpr int KSTEPS = BK / 32;
-    constexpr int TR_STEP = 2 * ((A_T ? MREP : 0) + (B_N ? NREP : 0));
-    static_assert(KSTEPS == 2 && TR_STEP <= 15, "lgkmcnt is a 4-bit count");
-    TrFrag atr[KSTEPS][MREP], btr[KSTEPS][NREP];
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      if (A_T)
-        for (int m = 0; m < MREP; ++m)
-          lay_issue(atr[ks][m], lds_addr(la), wr * WTM + m * 16, 32 * ks,
-                    lane);
-      if (B_N)
-        for (int n = 0; n < NREP; ++n)
-          lay_issue(btr[ks][n], lds_addr(lb), wc * WTN + n * 16, 32 * ks,
-                    lane);
-    }
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      const int kfrag = 32 * ks + 8 * (lane >> 4);
-      if (ks == 0)
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(TR_STEP) : "memory");
-      else
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      bf16x8 afrag[MREP], bfrag[NREP];
-      for (int m = 0; m < MREP; ++m) {
-        int row = wr * WTM + m * 16 + (lane & 15);
-        if (A_T)
-          afrag[m] = lay_take(atr[ks][m]);
-        else
-          afrag[m] = *(const bf16x8*)(la + lds_skew(row * BK + kfrag));
-      }
-      for (int n = 0; n < NREP; ++n) {
-        int col = wc * WTN + n * 16 + (lane & 15);
-        if (B_N)
-          bfrag[n] = lay_take(btr[ks][n]);
-        else
-          bfrag[n] = *(const bf16x8*)(lb + lds_skew(col * BK + kfrag));
-      }
-      for (int m = 0; m < MREP; ++m)
-        for (int n = 0; n < NREP; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[m], bfrag[n], acc[m][n], 0, 0, 0);
-    }
-    // every wave done READING buf[cur] before the next iteration's
-    // prefetch overwrites it — and, behind the last tile, before the
-    // epilogue's images do
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
+#define GEMM_LAY_LDA_KM (long)M
+#define GEMM_LAY_LDA_MK (long)K
+#define GEMM_LAY_LDB_KN (long)N
+#define GEMM_LAY_LDB_NK (long)K
+#define GEMM_LAY_K_FIRST 0
+#define GEMM_LAY_K_NEXT (long)(t + 1) * BK
+#define GEMM_LAY_TRIPS K / BK
+#include "include/gemm_bf16_lay_loop.inc"
 
   act_epilogue<ACT, MODE>(C, aux, bias, acc, lds, brow, bcol, N, tid, lane,
                           wr, wc);
@@ -518,12 +341,6 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_bf16_act(
   }
 }
 
-int tile_group() {
-  // tile order: row-major unless HPK_GEMM_GROUP asks for bands
-  const char* genv = std::getenv("HPK_GEMM_GROUP");
-  return genv ? std::atoi(genv) : 1;
-}
-
 struct ActArgs {
   void* C;
   void* aux;
@@ -542,22 +359,13 @@ void launch_act(const std::string& lay, const ActArgs& a) {
   const int tiles_n = (int)(a.N / BN);
   const int nwg = (int)(a.M / BM) * tiles_n;
   if (a.splits > 1) {
-    if (lay == "nt")
-      launch_gemm_splitk_bf16_nt_partials((float*)a.workspace, a.A, a.B, a.M,
-                                          a.N, a.K, a.splits, a.stream,
-                                          a.xcd_swizzle);
-    else
-      launch_gemm_bf16_layout_splitk_partials((float*)a.workspace, a.A, a.B,
-                                              a.M, a.N, a.K, lay.c_str(),
-                                              a.splits, a.stream,
-                                              a.xcd_swizzle);
-    const long nvec8 = a.M * a.N / 8;
-    long grid = nvec8 / 256;
-    if (grid > kSplitKReduceMaxGrid) grid = kSplitKReduceMaxGrid;
-    hipLaunchKernelGGL((k_splitk_reduce_bf16_act<ACT, MODE>),
-                       dim3((unsigned)grid), dim3(256), 0, a.stream,
-                       (u32x4*)a.C, (u32x4*)a.aux, (const f32x4*)a.workspace,
-                       a.bias, nvec8, a.splits, (int)a.N);
+    const unsigned grid = gemm_launch_splitk_partials(
+        (float*)a.workspace, a.A, a.B, a.M, a.N, a.K, lay.c_str(), a.splits,
+        a.stream, a.xcd_swizzle);
+    hipLaunchKernelGGL((k_splitk_reduce_bf16_act<ACT, MODE>), dim3(grid),
+                       dim3(256), 0, a.stream, (u32x4*)a.C, (u32x4*)a.aux,
+                       (const f32x4*)a.workspace, a.bias, a.M * a.N / 8,
+                       a.splits, (int)a.N);
     check_hip(hipGetLastError(), "launch_gemm_bf16_act(reduce)");
     return;
   }
@@ -566,7 +374,7 @@ void launch_act(const std::string& lay, const ActArgs& a) {
                        (__hip_bfloat16*)a.C, (__hip_bfloat16*)a.aux, a.bias,
                        (const __hip_bfloat16*)a.A, (const __hip_bfloat16*)a.B,
                        (int)a.M, (int)a.N, (int)a.K, tiles_n, nwg,
-                       a.xcd_swizzle, tile_group());
+                       a.xcd_swizzle, gemm_tile_group());
     check_hip(hipGetLastError(), "launch_gemm_bf16_act");
   };
   if (lay == "nt") return go(k_gemm_bf16_nt_act<ACT, MODE>);
@@ -582,20 +390,15 @@ void launch_gemm_bf16_act(void* C, void* aux, const void* A, const void* B,
                           const char* layout, int act, int mode, int splits,
                           void* workspace, hipStream_t stream,
                           int xcd_swizzle) {
-  const std::string lay = layout ? layout : "";
-  if (lay != "nt" && lay != "nn" && lay != "tn" && lay != "tt")
-    throw std::invalid_argument("gemm_bf16_act: unknown layout '" + lay +
-                                "' (nt|nn|tn|tt)");
+  gemm_parse_layout("gemm_bf16_act", layout, true); // throws unless valid
+  const std::string lay = layout;
   if (act != kActRelu && act != kActGelu)
     throw std::invalid_argument("gemm_bf16_act: unknown activation " +
                                 std::to_string(act));
   if (mode != kActForward && mode != kActGrad)
     throw std::invalid_argument("gemm_bf16_act: unknown mode " +
                                 std::to_string(mode));
-  if (M <= 0 || N <= 0 || K <= 0 || M % BM != 0 || N % BN != 0 ||
-      K % BK != 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-    throw std::runtime_error("gemm_bf16_act requires M,N % 128 == 0 and "
-                             "K % 64 == 0");
+  gemm_require_tile_shape("gemm_bf16_act", M, N, K);
   if (splits < 1 || splits > K / BK || splits > 65535)
     throw std::runtime_error(
         "gemm_bf16_act requires 1 <= splits <= K / 64 (" +

@@ -15,16 +15,17 @@
 // products S_h = Q_h K_h^T and O_h = P_h V_h and their backward products
 // need neither a loop over heads nor a contiguous() copy of each head.
 //
-// k_gemm_bf16_batched<A_T, B_N, Out> is the body of k_gemm_bf16_lay
-// (gemm_layout.hip), pasted: the 2x4 waves of 64x32, the prefetch of tile
-// t+1, the counted vmcnt / lgkmcnt, the raw barriers, 64 KiB LDS, the
-// lay_off image with ds_read_b64_tr_b16 reads. <false, false> is that body
-// with both operands K-contiguous, which is k_gemm_bf16_nt_db<2,4>'s operand
-// order (gemm.hip). The MFMAs see the same operands in the same order, so
-// with alpha == 1 the accumulators, and the fp32 C, are those kernels' bit
-// for bit. These are kernels of their own, not a stride switch inside the
-// parents: folding GEMM bodies changes the register allocation of the
-// kernels that exist (docs/findings.md #28).
+// k_gemm_bf16_batched<A_T, B_N, Out> runs the K loop of k_gemm_bf16_lay
+// (gemm_layout.hip), include/gemm_bf16_lay_loop.inc, with lda and ldb for
+// its row strides: the 2x4 waves of 64x32, the prefetch of tile t+1, the
+// counted vmcnt / lgkmcnt, the raw barriers, 64 KiB LDS, the lay_off image
+// with ds_read_b64_tr_b16 reads. <false, false> is that loop with both
+// operands K-contiguous, which is k_gemm_bf16_nt_db<2,4>'s operand order
+// (gemm.hip). The MFMAs see the same operands in the same order, so with
+// alpha == 1 the accumulators, and the fp32 C, are those kernels' bit for
+// bit. These are kernels of their own, not a stride switch inside the
+// parents: that changes the register allocation of the kernels that exist
+// (docs/findings.md #28).
 //
 // What differs is where a tile comes from and goes to. The grid is
 // (nwg, batch): blockIdx.x goes through hpk_tile_id per batch, blockIdx.y
@@ -51,6 +52,7 @@
 
 #include "include/hpk.h"
 #include "include/gemm_device.h"
+#include "include/gemm_host.h"
 #include "include/gemm_layout_device.h"
 
 #include <hip/hip_bf16.h>
@@ -62,18 +64,6 @@
 
 namespace hpk {
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef unsigned __attribute__((may_alias)) lds_u32;
-typedef u32x4 __attribute__((may_alias)) lds_u32x4;
-
-// bf16(lo) | bf16(hi) << 16, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 // fp32 C: the C/D mapping row = 4*(lane>>4)+r, col = lane&15, dword stores
 __device__ __forceinline__ void store_tile(float* __restrict__ C,
@@ -109,29 +99,7 @@ __device__ __forceinline__ void store_tile(__hip_bfloat16* __restrict__ C,
             pack_bf16(acc[m][n][r], acc[m][n][r + 1]);
     }
   __syncthreads();
-  // 2 passes x 512 threads x (2 rows x 8 columns)
-  for (int p = 0; p < 2; ++p) {
-    const GemmOutRead r0 = gemm_out_read(tid, p, 0);
-    const GemmOutRead r1 = gemm_out_read(tid, p, 1);
-    const u32x4 q0 =
-        *(const lds_u32x4*)(img + gemm_out_lds_offset(r0.row, r0.col));
-    const u32x4 q1 =
-        *(const lds_u32x4*)(img + gemm_out_lds_offset(r1.row, r1.col));
-    const bool odd_first = (tid >> 3) & 1;
-    const u32x4 ev = odd_first ? q1 : q0; // columns 8j .. 8j+3, both rows
-    const u32x4 od = odd_first ? q0 : q1; // columns 8j+4 .. 8j+7
-    const u32x4 top = {(ev[0] & 0xffffu) | (ev[1] << 16),
-                       (ev[2] & 0xffffu) | (ev[3] << 16),
-                       (od[0] & 0xffffu) | (od[1] << 16),
-                       (od[2] & 0xffffu) | (od[3] << 16)};
-    const u32x4 bot = {(ev[0] >> 16) | (ev[1] & 0xffff0000u),
-                       (ev[2] >> 16) | (ev[3] & 0xffff0000u),
-                       (od[0] >> 16) | (od[1] & 0xffff0000u),
-                       (od[2] >> 16) | (od[3] & 0xffff0000u)};
-    __hip_bfloat16* dst = C + (brow + r0.row) * ldc + bcol + 8 * (tid & 15);
-    *(u32x4*)dst = top;
-    *(u32x4*)(dst + ldc) = bot;
-  }
+  flush_tile(C, img, brow, bcol, ldc, tid);
 }
 
 // 8 waves as 2(M) x 4(N), 64x32 per wave. A_T: A_b is stored [K,M];
@@ -165,96 +133,14 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_batched(
   constexpr int ISSUES = TILE_HALF / (THREADS * 8);
   f32x4 acc[MREP][NREP] = {};
 
-  // lane-linear LDS write; the image is in the global chunk each lane takes
-  auto stage = [&](int buf, long k0) {
-    In* dst = lds + (long)buf * 2 * TILE_HALF;
-    for (int issue = 0; issue < ISSUES; ++issue) {
-      long o_base = (long)issue * elems_per_issue + (long)wid * (64 * 8);
-      // K-contiguous: [128 rows][64 k], skewed
-      long o = lds_unskew(o_base + (long)lane * 8);
-      int row = (int)(o / BK);
-      int kk = (int)(o % BK);
-      // X-contiguous: [64 k-rows][128 x]; slot = 16-byte chunk index
-      int slot = (int)(o_base / 8) + lane;
-      int krow = slot >> 4;
-      int x = 8 * ((slot & 15) ^ lay_key(krow));
-      const In* ga = A_T ? A + (k0 + krow) * lda + brow + x
-                         : A + (brow + row) * lda + k0 + kk;
-      const In* gb = B_N ? B + (k0 + krow) * ldb + bcol + x
-                         : B + (bcol + row) * ldb + k0 + kk;
-      glds16(ga, dst + o_base);
-      glds16(gb, dst + TILE_HALF + o_base);
-    }
-  };
-
-  stage(0, 0);
-  const int trips = K / BK;
-  for (int t = 0; t < trips; ++t) {
-    const int cur = t & 1;
-    const bool more = t + 1 < trips;
-    if (more) stage(cur ^ 1, (long)(t + 1) * BK);
-    // retire exactly the CURRENT tile's DMAs (2*ISSUES per thread, issued
-    // first; FIFO), leaving the prefetch in flight across the barrier
-    if (more)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ISSUES) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier(); // current buffer complete for all waves
-
-    const In* la = lds + (long)cur * 2 * TILE_HALF;
-    const In* lb = la + TILE_HALF;
-    // both k-steps' transposed reads are started at once; step 0 waits
-    // for all but step 1's (TR_STEP of them, the most recent), step 1
-    // for the rest. nt has none: TR_STEP == 0.
-    constexpr int KSTEPS = BK / 32;
-    constexpr int TR_STEP = 2 * ((A_T ? MREP : 0) + (B_N ? NREP : 0));
-    static_assert(KSTEPS == 2 && TR_STEP <= 15, "lgkmcnt is a 4-bit count");
-    TrFrag atr[KSTEPS][MREP], btr[KSTEPS][NREP];
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      if (A_T)
-        for (int m = 0; m < MREP; ++m)
-          lay_issue(atr[ks][m], lds_addr(la), wr * WTM + m * 16, 32 * ks,
-                    lane);
-      if (B_N)
-        for (int n = 0; n < NREP; ++n)
-          lay_issue(btr[ks][n], lds_addr(lb), wc * WTN + n * 16, 32 * ks,
-                    lane);
-    }
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      const int kfrag = 32 * ks + 8 * (lane >> 4);
-      if (A_T || B_N) {
-        if (ks == 0)
-          asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(TR_STEP) : "memory");
-        else
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      bf16x8 afrag[MREP], bfrag[NREP];
-      for (int m = 0; m < MREP; ++m) {
-        int row = wr * WTM + m * 16 + (lane & 15);
-        if (A_T)
-          afrag[m] = lay_take(atr[ks][m]);
-        else
-          afrag[m] = *(const bf16x8*)(la + lds_skew(row * BK + kfrag));
-      }
-      for (int n = 0; n < NREP; ++n) {
-        int col = wc * WTN + n * 16 + (lane & 15);
-        if (B_N)
-          bfrag[n] = lay_take(btr[ks][n]);
-        else
-          bfrag[n] = *(const bf16x8*)(lb + lds_skew(col * BK + kfrag));
-      }
-      for (int m = 0; m < MREP; ++m)
-        for (int n = 0; n < NREP; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[m], bfrag[n], acc[m][n], 0, 0, 0);
-    }
-    // every wave done READING buf[cur] before the next iteration's
-    // prefetch overwrites it — and, behind the last tile, before the
-    // bf16 epilogue's image does
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
+#define GEMM_LAY_LDA_KM lda
+#define GEMM_LAY_LDA_MK lda
+#define GEMM_LAY_LDB_KN ldb
+#define GEMM_LAY_LDB_NK ldb
+#define GEMM_LAY_K_FIRST 0
+#define GEMM_LAY_K_NEXT (long)(t + 1) * BK
+#define GEMM_LAY_TRIPS K / BK
+#include "include/gemm_bf16_lay_loop.inc"
 
   for (int m = 0; m < MREP; ++m)
     for (int n = 0; n < NREP; ++n) acc[m][n] = acc[m][n] * alpha;
@@ -272,9 +158,6 @@ struct BatchedArgs {
 
 template <bool A_T, bool B_N, typename Out>
 void launch_one(const char* label, const BatchedArgs& g) {
-  // tile order: row-major unless HPK_GEMM_GROUP asks for bands
-  const char* genv = std::getenv("HPK_GEMM_GROUP");
-  const int group = genv ? std::atoi(genv) : 1;
   const int tiles_n = (int)(g.N / BN);
   const int nwg = (int)(g.M / BM) * tiles_n;
   hipLaunchKernelGGL((k_gemm_bf16_batched<A_T, B_N, Out>),
@@ -282,7 +165,7 @@ void launch_one(const char* label, const BatchedArgs& g) {
                      (Out*)g.C, (const __hip_bfloat16*)g.A,
                      (const __hip_bfloat16*)g.B, (int)g.K, g.lda, g.bsA, g.ldb,
                      g.bsB, g.ldc, g.bsC, g.alpha, tiles_n, nwg, g.xcd_swizzle,
-                     group);
+                     gemm_tile_group());
   check_hip(hipGetLastError(), label);
 }
 
@@ -300,15 +183,8 @@ void launch_gemm_bf16_batched(void* C, int c_is_bf16, const void* A,
                               long bsB, long ldc, long bsC, const char* layout,
                               float alpha, hipStream_t stream,
                               int xcd_swizzle) {
-  const std::string lay = layout ? layout : "";
-  if (lay != "nt" && lay != "nn" && lay != "tn" && lay != "tt")
-    throw std::invalid_argument("gemm_bf16_batched: unknown layout '" + lay +
-                                "' (nt|nn|tn|tt)");
-  if (M <= 0 || N <= 0 || K <= 0 || M % BM != 0 || N % BN != 0 ||
-      K % BK != 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX ||
-      (M / BM) * (N / BN) > INT32_MAX)
-    throw std::runtime_error("gemm_bf16_batched requires M,N % 128 == 0 and "
-                             "K % 64 == 0");
+  const GemmLayout lay = gemm_parse_layout("gemm_bf16_batched", layout, true);
+  gemm_require_tile_shape("gemm_bf16_batched", M, N, K);
   if (batch < 1 || batch > kGemmBatchedMaxBatch)
     throw std::runtime_error("gemm_bf16_batched requires 1 <= batch <= 65535 "
                              "(got " + std::to_string(batch) + ")");
@@ -317,13 +193,13 @@ void launch_gemm_bf16_batched(void* C, int c_is_bf16, const void* A,
   if ((uintptr_t)A % 16 != 0 || (uintptr_t)B % 16 != 0)
     throw std::runtime_error("gemm_bf16_batched requires A and B on 16-byte "
                              "boundaries");
-  const bool a_t = lay[0] == 't', b_n = lay[1] == 'n';
   if (batch == 1) bsA = bsB = bsC = 0; // one image: the stride names nothing
   if (lda % 8 != 0 || ldb % 8 != 0 || bsA % 8 != 0 || bsB % 8 != 0)
     throw std::runtime_error("gemm_bf16_batched requires lda, ldb and the "
                              "batch strides of A and B to be multiples of 8 "
                              "elements");
-  if (lda < (a_t ? M : K) || ldb < (b_n ? N : K) || bsA < 0 || bsB < 0)
+  if (lda < (lay.a_t ? M : K) || ldb < (lay.b_n ? N : K) || bsA < 0 ||
+      bsB < 0)
     throw std::runtime_error("gemm_bf16_batched requires lda and ldb of at "
                              "least the stored row length and batch strides "
                              ">= 0");
@@ -344,13 +220,13 @@ void launch_gemm_bf16_batched(void* C, int c_is_bf16, const void* A,
 
   const BatchedArgs g{C, A, B, M, N, K, batch, lda, bsA, ldb, bsB, ldc, bsC,
                       alpha, stream, xcd_swizzle};
-  if (lay == "nt")
+  if (!lay.a_t && !lay.b_n)
     return launch_out<false, false>("launch_gemm_bf16_batched(nt)", c_is_bf16,
                                     g);
-  if (lay == "nn")
+  if (!lay.a_t)
     return launch_out<false, true>("launch_gemm_bf16_batched(nn)", c_is_bf16,
                                    g);
-  if (lay == "tn")
+  if (lay.b_n)
     return launch_out<true, true>("launch_gemm_bf16_batched(tn)", c_is_bf16,
                                   g);
   return launch_out<true, false>("launch_gemm_bf16_batched(tt)", c_is_bf16, g);

@@ -13,7 +13,9 @@
 // One body in the double-buffered 8-wave structure of
 // k_gemm_bf16_nt_db<2,4>: tile t+1's 16-byte global_load_lds DMAs are
 // issued before tile t is waited for, a counted vmcnt retires exactly
-// tile t, raw barriers, 64 KiB LDS, the same C/D epilogue.
+// tile t, raw barriers, 64 KiB LDS, the same C/D epilogue. The K loop is
+// include/gemm_bf16_lay_loop.inc, which the split-K, bf16-output,
+// activation and batched kernels of these layouts include as well.
 //
 // A K-contiguous operand is staged and read as in the NT kernels
 // (lds_skew image, ds_read_b128). An operand stored [K, X] (X = M or N
@@ -40,6 +42,7 @@
 
 #include "include/hpk.h"
 #include "include/gemm_device.h"
+#include "include/gemm_host.h"
 #include "include/gemm_layout_device.h"
 
 #include <hip/hip_bf16.h>
@@ -82,93 +85,14 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_lay(
   constexpr int ISSUES = TILE_HALF / (THREADS * 8);
   f32x4 acc[MREP][NREP] = {};
 
-  // lane-linear LDS write; the image is in the global chunk each lane takes
-  auto stage = [&](int buf, long k0) {
-    In* dst = lds + (long)buf * 2 * TILE_HALF;
-    for (int issue = 0; issue < ISSUES; ++issue) {
-      long o_base = (long)issue * elems_per_issue + (long)wid * (64 * 8);
-      // K-contiguous: [128 rows][64 k], skewed
-      long o = lds_unskew(o_base + (long)lane * 8);
-      int row = (int)(o / BK);
-      int kk = (int)(o % BK);
-      // X-contiguous: [64 k-rows][128 x]; slot = 16-byte chunk index
-      int slot = (int)(o_base / 8) + lane;
-      int krow = slot >> 4;
-      int x = 8 * ((slot & 15) ^ lay_key(krow));
-      const In* ga = A_T ? A + (k0 + krow) * (long)M + brow + x
-                         : A + (brow + row) * (long)K + k0 + kk;
-      const In* gb = B_N ? B + (k0 + krow) * (long)N + bcol + x
-                         : B + (bcol + row) * (long)K + k0 + kk;
-      glds16(ga, dst + o_base);
-      glds16(gb, dst + TILE_HALF + o_base);
-    }
-  };
-
-  stage(0, 0);
-  const int trips = K / BK;
-  for (int t = 0; t < trips; ++t) {
-    const int cur = t & 1;
-    const bool more = t + 1 < trips;
-    if (more) stage(cur ^ 1, (long)(t + 1) * BK);
-    // retire exactly the CURRENT tile's DMAs (2*ISSUES per thread, issued
-    // first; FIFO), leaving the prefetch in flight across the barrier
-    if (more)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ISSUES) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier(); // current buffer complete for all waves
-
-    const In* la = lds + (long)cur * 2 * TILE_HALF;
-    const In* lb = la + TILE_HALF;
-    // both k-steps' transposed reads are started at once; step 0 waits
-    // for all but step 1's (TR_STEP of them, the most recent), step 1
-    // for the rest
-    constexpr int KSTEPS = BK / 32;
-    constexpr int TR_STEP = 2 * ((A_T ? MREP : 0) + (B_N ? NREP : 0));
-    static_assert(KSTEPS == 2 && TR_STEP <= 15, "lgkmcnt is a 4-bit count");
-    TrFrag atr[KSTEPS][MREP], btr[KSTEPS][NREP];
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      if (A_T)
-        for (int m = 0; m < MREP; ++m)
-          lay_issue(atr[ks][m], lds_addr(la), wr * WTM + m * 16, 32 * ks,
-                    lane);
-      if (B_N)
-        for (int n = 0; n < NREP; ++n)
-          lay_issue(btr[ks][n], lds_addr(lb), wc * WTN + n * 16, 32 * ks,
-                    lane);
-    }
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      const int kfrag = 32 * ks + 8 * (lane >> 4);
-      if (ks == 0)
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(TR_STEP) : "memory");
-      else
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      bf16x8 afrag[MREP], bfrag[NREP];
-      for (int m = 0; m < MREP; ++m) {
-        int row = wr * WTM + m * 16 + (lane & 15);
-        if (A_T)
-          afrag[m] = lay_take(atr[ks][m]);
-        else
-          afrag[m] = *(const bf16x8*)(la + lds_skew(row * BK + kfrag));
-      }
-      for (int n = 0; n < NREP; ++n) {
-        int col = wc * WTN + n * 16 + (lane & 15);
-        if (B_N)
-          bfrag[n] = lay_take(btr[ks][n]);
-        else
-          bfrag[n] = *(const bf16x8*)(lb + lds_skew(col * BK + kfrag));
-      }
-      for (int m = 0; m < MREP; ++m)
-        for (int n = 0; n < NREP; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[m], bfrag[n], acc[m][n], 0, 0, 0);
-    }
-    // every wave done READING buf[cur] before the next iteration's
-    // prefetch overwrites it
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
+#define GEMM_LAY_LDA_KM (long)M
+#define GEMM_LAY_LDA_MK (long)K
+#define GEMM_LAY_LDB_KN (long)N
+#define GEMM_LAY_LDB_NK (long)K
+#define GEMM_LAY_K_FIRST 0
+#define GEMM_LAY_K_NEXT (long)(t + 1) * BK
+#define GEMM_LAY_TRIPS K / BK
+#include "include/gemm_bf16_lay_loop.inc"
 
   // C/D mapping row = 4*(lane>>4)+r, col = lane&15
   for (int m = 0; m < MREP; ++m)
@@ -183,15 +107,12 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_lay(
 template <bool A_T, bool B_N>
 void launch_lay(const char* label, float* C, const void* A, const void* B,
                 long M, long N, long K, hipStream_t stream, int xcd_swizzle) {
-  // tile order: row-major unless HPK_GEMM_GROUP asks for bands
-  const char* genv = std::getenv("HPK_GEMM_GROUP");
-  const int group = genv ? std::atoi(genv) : 1;
   const int tiles_n = (int)(N / BN);
   const int nwg = (int)(M / BM) * tiles_n;
   hipLaunchKernelGGL((k_gemm_bf16_lay<A_T, B_N>), dim3(nwg), dim3(512), 0,
                      stream, C, (const __hip_bfloat16*)A,
                      (const __hip_bfloat16*)B, (int)M, (int)N, (int)K, tiles_n,
-                     nwg, xcd_swizzle, group);
+                     nwg, xcd_swizzle, gemm_tile_group());
   check_hip(hipGetLastError(), label);
 }
 
@@ -200,26 +121,20 @@ void launch_lay(const char* label, float* C, const void* A, const void* B,
 void launch_gemm_bf16_layout(float* C, const void* A, const void* B, long M,
                              long N, long K, const char* layout,
                              hipStream_t stream, int xcd_swizzle) {
-  const std::string lay = layout ? layout : "";
-  if (lay == "nt")
+  if (layout != nullptr && std::string(layout) == "nt")
     throw std::invalid_argument("gemm_bf16_layout: layout 'nt' belongs to "
                                 "launch_gemm_bf16_nt");
-  if (lay != "nn" && lay != "tn" && lay != "tt")
-    throw std::invalid_argument("gemm_bf16_layout: unknown layout '" + lay +
-                                "' (nn|tn|tt)");
-  if (M <= 0 || N <= 0 || K <= 0 || M % BM != 0 || N % BN != 0 ||
-      K % BK != 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-    throw std::runtime_error("gemm_bf16_layout requires M,N % 128 == 0 and "
-                             "K % 64 == 0");
+  const GemmLayout lay = gemm_parse_layout("gemm_bf16_layout", layout, false);
+  gemm_require_tile_shape("gemm_bf16_layout", M, N, K);
   if (C == nullptr || A == nullptr || B == nullptr)
     throw std::runtime_error("gemm_bf16_layout: null operand");
   if ((uintptr_t)A % 16 != 0 || (uintptr_t)B % 16 != 0)
     throw std::runtime_error("gemm_bf16_layout requires A and B on 16-byte "
                              "boundaries");
-  if (lay == "nn")
+  if (!lay.a_t)
     return launch_lay<false, true>("launch_gemm_bf16_layout(nn)", C, A, B, M,
                                    N, K, stream, xcd_swizzle);
-  if (lay == "tn")
+  if (lay.b_n)
     return launch_lay<true, true>("launch_gemm_bf16_layout(tn)", C, A, B, M, N,
                                   K, stream, xcd_swizzle);
   return launch_lay<true, false>("launch_gemm_bf16_layout(tt)", C, A, B, M, N,

@@ -5,8 +5,10 @@
 // the tensors as stored, a weight-sized output and a sum over the tokens —
 // a 256x256 weight with 65536 tokens is 4 workgroups without the split.
 //
-// The kernel is the body of k_gemm_bf16_lay with the changes of
-// k_gemm_splitk_nt: grid (tiles, S), blockIdx.y = s walks only the K-tiles
+// The kernel is k_gemm_bf16_lay — the same K loop,
+// include/gemm_bf16_lay_loop.inc, given a first k and a trip count — with
+// the changes of k_gemm_splitk_nt: grid (tiles, S), blockIdx.y = s walks
+// only the K-tiles
 // gemm_splitk_ktiles() gives split s and writes its 128x128 partial to
 // slice s of a workspace [S][M][N]; launch_splitk_reduce_f32, behind it on
 // the same stream, folds the slices in ascending s. S == 1 writes C
@@ -17,8 +19,8 @@
 // the result is its bits on materialised transposes.
 //
 // It is a kernel of its own, not an S == 1 / S > 1 switch inside
-// k_gemm_bf16_lay: folding GEMM bodies changes the register allocation of
-// the kernels that exist (docs/findings.md #28).
+// k_gemm_bf16_lay: a switch inside a GEMM body changes the register
+// allocation of the kernels that exist (docs/findings.md #28).
 //
 // ds_read_b64_tr_b16 needs EXEC all ones: no divergent branch, no early
 // return, an exact grid, and trips >= 1 for every split because the
@@ -26,6 +28,7 @@
 
 #include "include/hpk.h"
 #include "include/gemm_device.h"
+#include "include/gemm_host.h"
 #include "include/gemm_layout_device.h"
 
 #include <hip/hip_bf16.h>
@@ -58,8 +61,8 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_lay_splitk(
   const long bcol = (long)(wg % tiles_n) * BN;
   const int s = (int)blockIdx.y;
   const SplitKRange range = gemm_splitk_ktiles(K / BK, S, s);
-  const long kbeg = range.first * BK; // this split's first k
-  const int trips = (int)range.count; // >= 1: the launcher keeps S <= K / 64
+  // this split's first k; range.count >= 1: the launcher keeps S <= K / 64
+  const long kbeg = range.first * BK;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
@@ -70,95 +73,14 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_lay_splitk(
   constexpr int ISSUES = TILE_HALF / (THREADS * 8);
   f32x4 acc[MREP][NREP] = {};
 
-  // lane-linear LDS write; the image is in the global chunk each lane
-  // takes. k0 is absolute: a [K, X] operand starts at ROW k0 with the full
-  // row stride, a K-contiguous one at column k0
-  auto stage = [&](int buf, long k0) {
-    In* dst = lds + (long)buf * 2 * TILE_HALF;
-    for (int issue = 0; issue < ISSUES; ++issue) {
-      long o_base = (long)issue * elems_per_issue + (long)wid * (64 * 8);
-      // K-contiguous: [128 rows][64 k], skewed
-      long o = lds_unskew(o_base + (long)lane * 8);
-      int row = (int)(o / BK);
-      int kk = (int)(o % BK);
-      // X-contiguous: [64 k-rows][128 x]; slot = 16-byte chunk index
-      int slot = (int)(o_base / 8) + lane;
-      int krow = slot >> 4;
-      int x = 8 * ((slot & 15) ^ lay_key(krow));
-      const In* ga = A_T ? A + (k0 + krow) * (long)M + brow + x
-                         : A + (brow + row) * (long)K + k0 + kk;
-      const In* gb = B_N ? B + (k0 + krow) * (long)N + bcol + x
-                         : B + (bcol + row) * (long)K + k0 + kk;
-      glds16(ga, dst + o_base);
-      glds16(gb, dst + TILE_HALF + o_base);
-    }
-  };
-
-  stage(0, kbeg);
-  for (int t = 0; t < trips; ++t) {
-    const int cur = t & 1;
-    const bool more = t + 1 < trips;
-    if (more) stage(cur ^ 1, kbeg + (long)(t + 1) * BK);
-    // retire exactly the CURRENT tile's DMAs (2*ISSUES per thread, issued
-    // first; FIFO), leaving the prefetch in flight across the barrier. A
-    // single-trip split takes the vmcnt(0) arm at once.
-    if (more)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ISSUES) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier(); // current buffer complete for all waves
-
-    const In* la = lds + (long)cur * 2 * TILE_HALF;
-    const In* lb = la + TILE_HALF;
-    // both k-steps' transposed reads are started at once; step 0 waits
-    // for all but step 1's (TR_STEP of them, the most recent), step 1
-    // for the rest
-    constexpr int KSTEPS = BK / 32;
-    constexpr int TR_STEP = 2 * ((A_T ? MREP : 0) + (B_N ? NREP : 0));
-    static_assert(KSTEPS == 2 && TR_STEP <= 15, "lgkmcnt is a 4-bit count");
-    TrFrag atr[KSTEPS][MREP], btr[KSTEPS][NREP];
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      if (A_T)
-        for (int m = 0; m < MREP; ++m)
-          lay_issue(atr[ks][m], lds_addr(la), wr * WTM + m * 16, 32 * ks,
-                    lane);
-      if (B_N)
-        for (int n = 0; n < NREP; ++n)
-          lay_issue(btr[ks][n], lds_addr(lb), wc * WTN + n * 16, 32 * ks,
-                    lane);
-    }
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      const int kfrag = 32 * ks + 8 * (lane >> 4);
-      if (ks == 0)
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(TR_STEP) : "memory");
-      else
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      bf16x8 afrag[MREP], bfrag[NREP];
-      for (int m = 0; m < MREP; ++m) {
-        int row = wr * WTM + m * 16 + (lane & 15);
-        if (A_T)
-          afrag[m] = lay_take(atr[ks][m]);
-        else
-          afrag[m] = *(const bf16x8*)(la + lds_skew(row * BK + kfrag));
-      }
-      for (int n = 0; n < NREP; ++n) {
-        int col = wc * WTN + n * 16 + (lane & 15);
-        if (B_N)
-          bfrag[n] = lay_take(btr[ks][n]);
-        else
-          bfrag[n] = *(const bf16x8*)(lb + lds_skew(col * BK + kfrag));
-      }
-      for (int m = 0; m < MREP; ++m)
-        for (int n = 0; n < NREP; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[m], bfrag[n], acc[m][n], 0, 0, 0);
-    }
-    // every wave done READING buf[cur] before the next iteration's
-    // prefetch overwrites it
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
+#define GEMM_LAY_LDA_KM (long)M
+#define GEMM_LAY_LDA_MK (long)K
+#define GEMM_LAY_LDB_KN (long)N
+#define GEMM_LAY_LDB_NK (long)K
+#define GEMM_LAY_K_FIRST kbeg
+#define GEMM_LAY_K_NEXT kbeg + (long)(t + 1) * BK
+#define GEMM_LAY_TRIPS (int)range.count
+#include "include/gemm_bf16_lay_loop.inc"
 
   // C/D mapping row = 4*(lane>>4)+r, col = lane&15, into slice s
   float* out = P + (long)s * M * N;
@@ -171,23 +93,22 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_lay_splitk(
     }
 }
 
-template <bool A_T, bool B_N>
-void launch_lay_splitk(const char* label, float* C, const void* A,
-                       const void* B, long M, long N, long K, int splits,
-                       void* workspace, hipStream_t stream, int xcd_swizzle) {
-  // tile order: row-major unless HPK_GEMM_GROUP asks for bands
-  const char* genv = std::getenv("HPK_GEMM_GROUP");
-  const int group = genv ? std::atoi(genv) : 1;
+// the tile kernel of layout `lay` on grid (tiles, splits), writing `out`
+void launch_tiles(const char* label, GemmLayout lay, float* out, const void* A,
+                  const void* B, long M, long N, long K, int splits,
+                  hipStream_t stream, int xcd_swizzle) {
   const int tiles_n = (int)(N / BN);
   const int nwg = (int)(M / BM) * tiles_n;
-  float* out = splits == 1 ? C : (float*)workspace;
-  hipLaunchKernelGGL((k_gemm_bf16_lay_splitk<A_T, B_N>), dim3(nwg, splits),
-                     dim3(512), 0, stream, out, (const __hip_bfloat16*)A,
-                     (const __hip_bfloat16*)B, (int)M, (int)N, (int)K, splits,
-                     tiles_n, nwg, xcd_swizzle, group);
-  check_hip(hipGetLastError(), label);
-  if (splits == 1) return;
-  launch_splitk_reduce_f32(C, workspace, M * N / 4, splits, stream);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nwg, splits), dim3(512), 0, stream, out,
+                       (const __hip_bfloat16*)A, (const __hip_bfloat16*)B,
+                       (int)M, (int)N, (int)K, splits, tiles_n, nwg,
+                       xcd_swizzle, gemm_tile_group());
+    check_hip(hipGetLastError(), label);
+  };
+  if (!lay.a_t) return go(k_gemm_bf16_lay_splitk<false, true>);
+  if (lay.b_n) return go(k_gemm_bf16_lay_splitk<true, true>);
+  go(k_gemm_bf16_lay_splitk<true, false>);
 }
 
 } // namespace
@@ -197,17 +118,12 @@ void launch_gemm_bf16_layout_splitk(float* C, const void* A, const void* B,
                                     const char* layout, int splits,
                                     void* workspace, hipStream_t stream,
                                     int xcd_swizzle) {
-  const std::string lay = layout ? layout : "";
-  if (lay == "nt")
+  if (layout != nullptr && std::string(layout) == "nt")
     throw std::invalid_argument("gemm_bf16_layout_splitk: layout 'nt' "
                                 "belongs to launch_gemm_splitk_bf16_nt");
-  if (lay != "nn" && lay != "tn" && lay != "tt")
-    throw std::invalid_argument("gemm_bf16_layout_splitk: unknown layout '" +
-                                lay + "' (nn|tn|tt)");
-  if (M <= 0 || N <= 0 || K <= 0 || M % BM != 0 || N % BN != 0 ||
-      K % BK != 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-    throw std::runtime_error("gemm_bf16_layout_splitk requires M,N % 128 == 0 "
-                             "and K % 64 == 0");
+  const GemmLayout lay =
+      gemm_parse_layout("gemm_bf16_layout_splitk", layout, false);
+  gemm_require_tile_shape("gemm_bf16_layout_splitk", M, N, K);
   if (splits < 1 || splits > K / BK || splits > 65535)
     throw std::runtime_error(
         "gemm_bf16_layout_splitk requires 1 <= splits <= K / 64 (" +
@@ -224,17 +140,12 @@ void launch_gemm_bf16_layout_splitk(float* C, const void* A, const void* B,
     throw std::runtime_error("gemm_bf16_layout_splitk requires C and the "
                              "workspace on 16-byte boundaries when "
                              "splits > 1");
-  if (lay == "nn")
-    return launch_lay_splitk<false, true>(
-        "launch_gemm_bf16_layout_splitk(nn)", C, A, B, M, N, K, splits,
-        workspace, stream, xcd_swizzle);
-  if (lay == "tn")
-    return launch_lay_splitk<true, true>(
-        "launch_gemm_bf16_layout_splitk(tn)", C, A, B, M, N, K, splits,
-        workspace, stream, xcd_swizzle);
-  return launch_lay_splitk<true, false>(
-      "launch_gemm_bf16_layout_splitk(tt)", C, A, B, M, N, K, splits,
-      workspace, stream, xcd_swizzle);
+  const std::string label =
+      std::string("launch_gemm_bf16_layout_splitk(") + layout + ")";
+  launch_tiles(label.c_str(), lay, splits == 1 ? C : (float*)workspace, A, B,
+               M, N, K, splits, stream, xcd_swizzle);
+  if (splits == 1) return;
+  launch_splitk_reduce_f32(C, workspace, M * N / 4, splits, stream);
 }
 
 // The tile kernel alone, for a caller that folds the slices itself
@@ -244,14 +155,9 @@ void launch_gemm_bf16_layout_splitk_partials(float* workspace, const void* A,
                                              long K, const char* layout,
                                              int splits, hipStream_t stream,
                                              int xcd_swizzle) {
-  const std::string lay = layout ? layout : "";
-  if (lay != "nn" && lay != "tn" && lay != "tt")
-    throw std::invalid_argument("gemm_bf16_layout_splitk_partials: unknown "
-                                "layout '" + lay + "' (nn|tn|tt)");
-  if (M <= 0 || N <= 0 || K <= 0 || M % BM != 0 || N % BN != 0 ||
-      K % BK != 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-    throw std::runtime_error("gemm_bf16_layout_splitk_partials requires "
-                             "M,N % 128 == 0 and K % 64 == 0");
+  const GemmLayout lay =
+      gemm_parse_layout("gemm_bf16_layout_splitk_partials", layout, false);
+  gemm_require_tile_shape("gemm_bf16_layout_splitk_partials", M, N, K);
   if (splits < 2 || splits > K / BK || splits > 65535)
     throw std::runtime_error("gemm_bf16_layout_splitk_partials requires "
                              "2 <= splits <= K / 64");
@@ -261,26 +167,8 @@ void launch_gemm_bf16_layout_splitk_partials(float* workspace, const void* A,
       (uintptr_t)workspace % 16 != 0)
     throw std::runtime_error("gemm_bf16_layout_splitk_partials requires A, B "
                              "and the workspace on 16-byte boundaries");
-  const char* genv = std::getenv("HPK_GEMM_GROUP");
-  const int group = genv ? std::atoi(genv) : 1;
-  const int tiles_n = (int)(N / BN);
-  const int nwg = (int)(M / BM) * tiles_n;
-  const dim3 grid(nwg, splits);
-  const __hip_bfloat16* a = (const __hip_bfloat16*)A;
-  const __hip_bfloat16* b = (const __hip_bfloat16*)B;
-  if (lay == "nn")
-    hipLaunchKernelGGL((k_gemm_bf16_lay_splitk<false, true>), grid, dim3(512),
-                       0, stream, workspace, a, b, (int)M, (int)N, (int)K,
-                       splits, tiles_n, nwg, xcd_swizzle, group);
-  else if (lay == "tn")
-    hipLaunchKernelGGL((k_gemm_bf16_lay_splitk<true, true>), grid, dim3(512),
-                       0, stream, workspace, a, b, (int)M, (int)N, (int)K,
-                       splits, tiles_n, nwg, xcd_swizzle, group);
-  else
-    hipLaunchKernelGGL((k_gemm_bf16_lay_splitk<true, false>), grid, dim3(512),
-                       0, stream, workspace, a, b, (int)M, (int)N, (int)K,
-                       splits, tiles_n, nwg, xcd_swizzle, group);
-  check_hip(hipGetLastError(), "launch_gemm_bf16_layout_splitk_partials");
+  launch_tiles("launch_gemm_bf16_layout_splitk_partials", lay, workspace, A, B,
+               M, N, K, splits, stream, xcd_swizzle);
 }
 
 } // namespace hpk

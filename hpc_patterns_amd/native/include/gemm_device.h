@@ -1,12 +1,18 @@
 // gemm_device.h — device helpers shared by the K7 GEMM translation units
-// (gemm.hip, gemm_splitk.hip): vector typedefs, the 128^2-tile constants,
-// the LDS skews, the tile order (hpk_group_remap, hpk_tile_id) and the
-// global_load_lds wrappers. Everything sits in an anonymous namespace, so
-// each translation unit gets its own internal copy, exactly as when these
-// lived at the top of gemm.hip (the move left gemm.hip's device code
-// byte-identical: profiles/gemm_splitk.md).
+// (gemm*.hip): vector typedefs, the bf16 pack and unpack, the 128^2-tile
+// constants, the LDS skews, the tile order (hpk_group_remap, hpk_tile_id),
+// the global_load_lds wrappers and the store of a staged bf16 tile
+// (flush_tile). Everything sits in an anonymous namespace, so each
+// translation unit gets its own internal copy, exactly as when these lived
+// in the .hip files (every move left the device code identical:
+// profiles/gemm_splitk.md, profiles/gemm_loop_fold.md). The K loops the
+// kernels share are text, not functions: gemm_bf16_nt_loop.inc and
+// gemm_bf16_lay_loop.inc.
 #pragma once
 
+#include "hpk.h"
+
+#include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
 namespace hpk {
@@ -18,6 +24,25 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(16))) int i32x16;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+// what a staged bf16 tile in LDS (an In[] array) is written and read as
+typedef unsigned __attribute__((may_alias)) lds_u32;
+typedef u32x4 __attribute__((may_alias)) lds_u32x4;
+
+// bf16(lo) | bf16(hi) << 16, round to nearest even (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
+  const f32x2 v = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+// the two halves of such a dword, widened (exact)
+__device__ __forceinline__ float bf16_lo(unsigned d) {
+  return __builtin_bit_cast(float, d << 16);
+}
+__device__ __forceinline__ float bf16_hi(unsigned d) {
+  return __builtin_bit_cast(float, d & 0xffff0000u);
+}
 
 constexpr int BM = 128, BN = 128, BK = 64;
 
@@ -118,6 +143,41 @@ __device__ __forceinline__ void glds4(const void* g, void* l) {
   __builtin_amdgcn_global_load_lds(
       (const __attribute__((address_space(1))) void*)g,
       (__attribute__((address_space(3))) void*)l, 4, 0, 0);
+}
+
+// A staged bf16 tile (the image of gemm_out_lds_offset, hpk.h) from LDS at
+// `img` to the 128x128 tile of `dst` at (brow, bcol), row stride ld (int or
+// long): 2 passes x 512 threads x (2 rows x 8 columns), every thread two
+// 16-byte LDS reads, 8 bit operations to separate the two rows and two
+// 16-byte stores, so 16 lanes write one whole 256-byte row. Behind the
+// barrier that completes the image.
+template <typename Ld>
+__device__ __forceinline__ void flush_tile(__hip_bfloat16* __restrict__ dst,
+                                           const char* img, long brow,
+                                           long bcol, Ld ld, int tid) {
+  for (int p = 0; p < 2; ++p) {
+    const GemmOutRead r0 = gemm_out_read(tid, p, 0);
+    const GemmOutRead r1 = gemm_out_read(tid, p, 1);
+    const u32x4 q0 =
+        *(const lds_u32x4*)(img + gemm_out_lds_offset(r0.row, r0.col));
+    const u32x4 q1 =
+        *(const lds_u32x4*)(img + gemm_out_lds_offset(r1.row, r1.col));
+    const bool odd_first = (tid >> 3) & 1;
+    const u32x4 ev = odd_first ? q1 : q0; // columns 8j .. 8j+3, both rows
+    const u32x4 od = odd_first ? q0 : q1; // columns 8j+4 .. 8j+7
+    const u32x4 top = {(ev[0] & 0xffffu) | (ev[1] << 16),
+                       (ev[2] & 0xffffu) | (ev[3] << 16),
+                       (od[0] & 0xffffu) | (od[1] << 16),
+                       (od[2] & 0xffffu) | (od[3] << 16)};
+    const u32x4 bot = {(ev[0] >> 16) | (ev[1] & 0xffff0000u),
+                       (ev[2] >> 16) | (ev[3] & 0xffff0000u),
+                       (od[0] >> 16) | (od[1] & 0xffff0000u),
+                       (od[2] >> 16) | (od[3] & 0xffff0000u)};
+    __hip_bfloat16* d =
+        dst + (brow + r0.row) * (long)ld + bcol + 8 * (tid & 15);
+    *(u32x4*)d = top;
+    *(u32x4*)(d + ld) = bot;
+  }
 }
 
 } // namespace

@@ -1,5 +1,7 @@
 // gemm_layout_device.h — device helpers shared by the translation units of
-// the nn/tn/tt operand layouts (gemm_layout.hip, gemm_layout_splitk.hip):
+// the nn/tn/tt operand layouts (gemm_layout.hip, gemm_layout_splitk.hip,
+// gemm_epilogue.hip, gemm_act.hip, gemm_batched.hip) and used by their K
+// loop, gemm_bf16_lay_loop.inc:
 // the [64 k-rows][128 x] LDS image of an operand stored [K, X] (lay_key,
 // lay_off) and its transposed reads (TrFrag, lay_issue, lay_take,
 // lds_addr). Everything sits in an anonymous namespace, so each translation
