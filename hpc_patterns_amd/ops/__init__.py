@@ -4,12 +4,16 @@ Python face of the native kernels in native/kernels.hip (the MI355X
 equivalents of the reference's device-code sites). All
 functions launch on the CURRENT torch CUDA stream unless given one, and all
 REQUIRE the native extension when a GPU is present — no silent eager
-fallback.
+fallback. A function given stream= issues ALL its device work — pads,
+casts, copies and allocations as well as kernels — on that stream
+(docs/gemm.md, "Streams").
 """
 
 from __future__ import annotations
 
+import contextlib
 import functools
+import inspect
 
 import torch
 
@@ -20,6 +24,38 @@ def _stream_handle(stream=None) -> int:
     if stream is not None:
         return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
     return torch.cuda.current_stream().cuda_stream
+
+
+_NO_SWITCH = contextlib.nullcontext()
+
+
+def _on(stream):
+    """Context that makes `stream` torch's current stream, so that torch ops
+    and the caching allocator follow the kernels (docs/gemm.md, "Streams").
+    None — and a stream that is current already — switch nothing. A raw
+    handle, as _stream_handle takes it, is wrapped in an ExternalStream."""
+    if stream is None:
+        return _NO_SWITCH
+    if not hasattr(stream, "cuda_stream"):
+        stream = torch.cuda.ExternalStream(int(stream))
+    if stream.cuda_stream == torch.cuda.current_stream().cuda_stream:
+        return _NO_SWITCH
+    return torch.cuda.stream(stream)
+
+
+def _body_on_stream(fn):
+    """Run the whole of fn under _on(its stream argument); stream=None calls
+    fn as it is."""
+    pos = list(inspect.signature(fn).parameters).index("stream")
+
+    @functools.wraps(fn)
+    def on_stream(*args, **kwargs):
+        stream = args[pos] if len(args) > pos else kwargs.get("stream")
+        if stream is None:
+            return fn(*args, **kwargs)
+        with _on(stream):
+            return fn(*args, **kwargs)
+    return on_stream
 
 
 def _check_f32(t: torch.Tensor, name: str):
@@ -365,11 +401,9 @@ def gemm_splitk(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
         if c.data_ptr() % 16 != 0:
             raise ValueError("c must start on a 16-byte boundary")
         if workspace is None:
-            workspace = torch.empty(splits, m, n, dtype=c.dtype,
-                                    device=c.device)
-            if hasattr(stream, "cuda_stream"):
-                # allocated on the current stream, used on another
-                workspace.record_stream(stream)
+            with _on(stream):   # from the pool of the stream that uses it
+                workspace = torch.empty(splits, m, n, dtype=c.dtype,
+                                        device=c.device)
         ws_ptr = workspace.data_ptr()
     getattr(native(), f"gemm_splitk_{kind}_nt")(
         c.data_ptr(), a.data_ptr(), b.data_ptr(), m, n, k, splits, ws_ptr,
@@ -419,6 +453,7 @@ def _pad2d(t: torch.Tensor, rows: int, cols: int, fill=0):
     return out
 
 
+@_body_on_stream
 def matmul_nt(a: torch.Tensor, b: torch.Tensor,
               a_scale: torch.Tensor = None, b_scale: torch.Tensor = None,
               stream=None, xcd_swizzle: bool = False,
@@ -612,6 +647,7 @@ def dequantize_mx(q: torch.Tensor, scale: torch.Tensor, fmt: str) -> torch.Tenso
     return (v.view(rows, k // 32, 32) * factor.unsqueeze(-1)).view(rows, k)
 
 
+@_body_on_stream
 def quantize_mx(x: torch.Tensor, fmt: str, stream=None):
     """Convert-to-MX on the GPU (native/quant.hip): fp32 or bf16 [rows, K]
     -> (q, scale), exactly the operands gemm_mxfp8 / gemm_mxfp4 take.
@@ -651,6 +687,7 @@ def quantize_mx(x: torch.Tensor, fmt: str, stream=None):
     return q, scale
 
 
+@_body_on_stream
 def matmul_mx(a: torch.Tensor, b: torch.Tensor, fmt: str = "mxfp8",
               stream=None) -> torch.Tensor:
     """A @ B^T through the MX GEMMs from real tensors: a [M,K], b [N,K],
@@ -817,11 +854,9 @@ def gemm_bf16_layout_splitk(c: torch.Tensor, a: torch.Tensor,
         if c.data_ptr() % 16 != 0:
             raise ValueError("c must start on a 16-byte boundary")
         if workspace is None:
-            workspace = torch.empty(splits, m, n, dtype=c.dtype,
-                                    device=c.device)
-            if hasattr(stream, "cuda_stream"):
-                # allocated on the current stream, used on another
-                workspace.record_stream(stream)
+            with _on(stream):   # from the pool of the stream that uses it
+                workspace = torch.empty(splits, m, n, dtype=c.dtype,
+                                        device=c.device)
         ws_ptr = workspace.data_ptr()
     native().gemm_bf16_layout_splitk(
         c.data_ptr(), a.data_ptr(), b.data_ptr(), m, n, k, layout, splits,
@@ -985,11 +1020,9 @@ def gemm_bf16_epilogue(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
     ws_ptr = 0
     if splits > 1:
         if workspace is None:
-            workspace = torch.empty(splits, m, n, dtype=torch.float32,
-                                    device=c.device)
-            if hasattr(stream, "cuda_stream"):
-                # allocated on the current stream, used on another
-                workspace.record_stream(stream)
+            with _on(stream):   # from the pool of the stream that uses it
+                workspace = torch.empty(splits, m, n, dtype=torch.float32,
+                                        device=c.device)
         ws_ptr = workspace.data_ptr()
     native().gemm_bf16_epilogue(
         c.data_ptr(), a.data_ptr(), b.data_ptr(), bias_ptr, m, n, k, layout,
@@ -1006,6 +1039,7 @@ def colsum_plan(m: int, n: int, n_cu: int = None) -> int:
     return native().colsum_plan(int(m), int(n), int(n_cu))
 
 
+@_body_on_stream
 def colsum_bf16(x: torch.Tensor, out: torch.Tensor = None,
                 stream=None) -> torch.Tensor:
     """out[n] = sum_m x[m, n] in fp32 for a bf16 [M, N] contiguous CUDA
@@ -1046,9 +1080,6 @@ def colsum_bf16(x: torch.Tensor, out: torch.Tensor = None,
     buf = torch.empty(width * (0 if direct else 1)
                       + (pitch * chunks if chunks > 1 else 0),
                       dtype=torch.float32, device=x.device)
-    if hasattr(stream, "cuda_stream"):
-        buf.record_stream(stream)
-        xp.record_stream(stream)
     res = out if direct else buf[:width]
     ws_ptr = buf[0 if direct else width:].data_ptr() if chunks > 1 else 0
     lib.colsum_bf16(res.data_ptr(), xp.data_ptr(), m, n8, chunks, ws_ptr,
@@ -1056,11 +1087,7 @@ def colsum_bf16(x: torch.Tensor, out: torch.Tensor = None,
     if direct:
         return out
     if out is not None:
-        if hasattr(stream, "cuda_stream"):
-            with torch.cuda.stream(stream):
-                out.copy_(buf[:n])
-        else:
-            out.copy_(buf[:n])
+        out.copy_(buf[:n])
         return out
     return buf[:n]
 
@@ -1211,11 +1238,9 @@ def gemm_bf16_act(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
     ws_ptr = 0
     if splits > 1:
         if workspace is None:
-            workspace = torch.empty(splits, m, n, dtype=torch.float32,
-                                    device=c.device)
-            if hasattr(stream, "cuda_stream"):
-                # allocated on the current stream, used on another
-                workspace.record_stream(stream)
+            with _on(stream):   # from the pool of the stream that uses it
+                workspace = torch.empty(splits, m, n, dtype=torch.float32,
+                                        device=c.device)
         ws_ptr = workspace.data_ptr()
     lib = native()
     lib.gemm_bf16_act(
@@ -1255,6 +1280,7 @@ def _check_activation_keywords(activation, return_aux, activation_grad,
         raise ValueError("activation_grad takes no bias")
 
 
+@_body_on_stream
 def matmul(a: torch.Tensor, b: torch.Tensor, stream=None,
            xcd_swizzle: bool = False, split_k=None, out_dtype=None,
            bias: torch.Tensor = None, activation=None,
@@ -1837,6 +1863,7 @@ def _bmm_operand(t: torch.Tensor, rows: int, cols: int, row_mult: int,
     return out.expand(batch, rows, cols) if once else out
 
 
+@_body_on_stream
 def bmm(a: torch.Tensor, b: torch.Tensor, out_dtype=None, alpha=1.0,
         stream=None) -> torch.Tensor:
     """Batched front door: alpha * (a [B,M,K] @ b [B,K,N]) for bf16 a, b of
